@@ -15,12 +15,15 @@ Multi-GPU (one process per GPU, torchrun): the batch is sharded across ranks
 (weak scaling, `--batch-per-gpu` items each); rank 0 broadcasts the conditioning
 once over RCCL before the timed region; no collective inside it.
 
-Prints ONE JSON line on rank 0 (driver contract), with `roofline` for the
+Prints ONE JSON line on rank 0 (driver contract).  A plain run sets up, warms up, times `--steps` steps
+(`ms_per_step` = the timed region / `--steps`), writes the latents the loop left if `--dump-outputs DIR`
+asks for them (the inputs are seeded: the same arguments give the same inputs in every run) and prints
+the headline.  `--full` adds everything below: `roofline` for the
 dominant kernel (the MLP gate|up GEMM, measured with HIP events on the launch
 stream) and `cpu_baseline` (oracle/cpu/dit_cpu.cpp, the C++/OpenMP restatement of ggml's CPU
 forward_dit, on the host cores: one 240 s forward plus the configs[0] 10 s F16 forward).
 
-Extra lines beside the headline (one GPU only; each the same 27-step schedule, timed the same way):
+Extra lines beside the headline (`--full`, one GPU only; each the same 27-step schedule, timed the same way):
   hook_line        the reference pipeline's drop-in path: a Python Euler loop over torch ROCm tensors calling
                    the installed `decoder.forward` (acestep_mi355x.hook, scripts/run_non_ggml_real_case.py:
                    460-533) once per step, as model.generate_audio does
@@ -86,10 +89,20 @@ def parse():
                     help="skip the bf16-weight run that is reported beside a quantized line")
     ap.add_argument("--no-extra-lines", action="store_true",
                     help="skip hook_line / attn_split_line / line_10s / line_60s")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: per-kernel breakdown and rooflines, the extra "
+                         "lines, the bf16 line and the CPU baseline (each can be skipped with its --no-* option); "
+                         "without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the latents the sampling loop left (what its caller receives) "
+                         "as float32 DIR/latents.npy (DIR/latents_rank<r>.npy under torchrun)")
     ap.add_argument("--emulate", action="store_true",
                     help="TEST MODE: the multi-rank code path on CPU (gloo, the host-emulated library of tests/, "
                          "tiny config); its numbers are not a measurement")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline = args.no_profile = args.no_bf16_line = args.no_extra_lines = True
+    return args
 
 
 def main():
@@ -134,12 +147,13 @@ def main():
     else:
         cfg = make_config()
         lib_path = None
-    # rank 0 writes the synthetic checkpoint, the others wait for it
+    # rank 0 writes the synthetic checkpoint (or finds it in the cache), the others wait for it
+    synth_root = None if args.emulate else synth_cache_root()
     if rank == 0:
-        ckpt = cached_checkpoint(cfg, seed=0, backend="torch")
+        ckpt = cached_checkpoint(cfg, seed=0, backend="torch", root=synth_root)
     barrier()
     if rank != 0:
-        ckpt = cached_checkpoint(cfg, seed=0, backend="torch")
+        ckpt = cached_checkpoint(cfg, seed=0, backend="torch", root=synth_root)
 
     if args.qtype == "bf16":
         args.qtype = ""
@@ -267,6 +281,8 @@ def main():
     # conditioning broadcast to every rank before the timed region (f32 noise, context, encoder states)
     bcast_bytes = 4 * B * (T * audio + T * ctxd + L * H)
     finite = bool(torch.isfinite(xt).all().item())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "latents" if world == 1 else f"latents_rank{rank}", xt)
     memory = {"weights_bytes": mem_weights, "workspace_bytes": dev_used() - mem0 - mem_weights,
               "stage_scope": stage_scope if args.qtype else None}
 
@@ -535,6 +551,41 @@ def main():
     br.close()
     if world > 1:
         dist.destroy_process_group()
+
+
+def synth_cache_root():
+    """Where the workload's 3 GB synthetic checkpoint is cached: ACE_MI_SYNTH_DIR, else the per-user cache directory
+    (build() of __graft_entry__ fills it through workload_checkpoint(), so a bench run does not spend its first
+    seconds drawing 1.5 G random weights), else None = cached_checkpoint's default under the temp directory."""
+    if os.environ.get("ACE_MI_SYNTH_DIR"):
+        return None
+    root = os.path.join(os.path.expanduser("~"), ".cache", "acestep_mi355x_synth")
+    try:
+        os.makedirs(root, exist_ok=True)
+    except OSError:
+        return None
+    return root if os.access(root, os.W_OK) else None
+
+
+def workload_checkpoint():
+    """The default workload's checkpoint (the full DiT config, seed 0, bf16), written once into synth_cache_root()."""
+    from acestep_mi355x.synthetic import cached_checkpoint, make_config
+    return cached_checkpoint(make_config(), seed=0, backend="torch", root=synth_cache_root())
+
+
+DUMP_MAX_BYTES = 48 << 20
+
+
+def dump_outputs(out_dir, name, x):
+    """The timed loop's result (the latents after warmup + steps Euler steps, updated in place) as float32
+    out_dir/name.npy; above DUMP_MAX_BYTES a fixed seeded sample of its elements (sorted flat indices)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = x.detach().float().cpu().numpy()
+    cap = DUMP_MAX_BYTES // 4
+    if a.size > cap:
+        a = a.reshape(-1)[np.sort(np.random.default_rng(0).integers(0, a.size, size=cap))]
+    np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def attention_breakdown(br, run, steps, sync):

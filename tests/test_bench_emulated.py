@@ -18,6 +18,39 @@ def _free_port():
         return s.getsockname()[1]
 
 
+def _plain_run(out_dir, steps):
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--emulate", "--gpus", "1", "--steps", str(steps),
+           "--warmup", "1", "--seconds", "2", "--enc-len", "16", "--qtype", "bf16", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=dict(os.environ, OMP_NUM_THREADS="1"),
+                       cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_plain_run_dumps_the_timed_loops_latents(tmp_path):
+    """A plain run (no --full) reports the headline only, --steps sets the timed steps behind ms_per_step, and
+    --dump-outputs writes the float32 latents the loop left: identical between two runs with the same arguments,
+    different after another number of steps."""
+    import numpy as np
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from hostlib import CLANG
+    if not os.path.exists(CLANG):
+        pytest.skip("host clang++ not available")
+    d = [_plain_run(tmp_path / n, k) for n, k in (("a", 3), ("b", 3), ("c", 2))]
+    for line, k in zip(d, (3, 3, 2)):
+        assert line["steps"] == k and line["warmup"] == 1 and line["finite"] is True
+        assert line["ms_per_step"] == pytest.approx(1000.0 * line["ranks"]["elapsed_s"][0] / k, rel=1e-3, abs=5e-3)
+        assert line["value"] == pytest.approx(1000.0 / line["ms_per_step"], rel=1e-3)
+        assert line["roofline"] is None and line["cpu_baseline"] is None and line["bf16_line"] is None
+        assert line["breakdown"] == {} and "hook_line" not in line
+    a, b, c = (np.load(tmp_path / n / "latents.npy") for n in "abc")
+    assert a.dtype == np.float32 and a.shape == (1, 50, 64) and np.isfinite(a).all()
+    assert np.array_equal(a, b)
+    assert not np.array_equal(a, c)
+
+
 @pytest.mark.parametrize("world,bpg", [(2, 1), (4, 2), (8, 1)])
 def test_bench_multi_rank_path_emulated(world, bpg):
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))

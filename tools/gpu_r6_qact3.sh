@@ -7,5 +7,5 @@ timeout -k 10 300 $P tests/test_gpu_kernels.py -k attention > $out/test_attn.log
 timeout -k 10 600 $P tests/test_gpu_quant.py -k "full_width_vs_ggml" > $out/test_quant_fw.log 2>&1; rc=$?; echo "rc=$rc" >> $out/test_quant_fw.log; [ $rc -gt 1 ] && exit $rc
 timeout -k 10 600 $P tests/test_gpu_configs.py -k "quantized_configs" > $out/test_configs_q.log 2>&1; rc=$?; echo "rc=$rc" >> $out/test_configs_q.log; [ $rc -gt 1 ] && exit $rc
 timeout -k 10 300 python -u tools/qact_bench.py > $out/qact_bf16.jsonl 2> $out/qact_bf16.err || exit $?
-timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || exit $?
+timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.err || exit $?
 exit 0

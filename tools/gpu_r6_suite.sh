@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"; export TMPDIR=/tmp
 bash tools/gpu_tests.sh; rc=$?
 [ $rc -gt 1 ] && exit $rc
 if [ -n "$BENCH" ]; then
-  mkdir -p gpurun_out/bench
-  timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 > gpurun_out/bench/bench.json 2> gpurun_out/bench/bench.err || exit $?
+  bout=${OUT:-bench_outputs}/bench; mkdir -p "$bout"
+  timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 > "$bout/bench.json" 2> "$bout/bench.err" || exit $?
 fi
 exit $rc
