@@ -109,7 +109,7 @@ void launch_dequant_bf16_batch(const DequantJob* jobs, int n, hipStream_t s);
 // ggml's mul_mat against a quantized weight first converts the f32 activation rows to the weight's vec_dot_type
 // (Q8_0 blocks for Q8_0 weights, Q8_K for K-quants) and takes integer dot products per block
 // (ggml-metal-embed.metal:222-227, 3110-3128; ggml-cpu quantize_row_q8_0 / quantize_row_q8_K_ref / vec_dot_*).
-// ACE_MI_QUANT_ACT=q8 runs the DiT that way (DitEngine::forward_qact).
+// ACE_MI_QUANT_ACT=q8 runs the DiT that way (the QACT arm of DitEngine::walk, runtime/engine_qact.cpp).
 // Activation blocks on the device: q int8 [M][K]; s f32 [K/32][ld_s] per 32-value block (Q8_0: fp16(d);
 // Q8_K: the 256-block's d in each of its eight 32-blocks); bsum f32 [K/32][ld_s] = sum of the block's q (Q8_K
 // only: the Q4_K min term).  ld_s >= M rounded up to 128 (the GEMM reads whole 128-row tiles of s / bsum).

@@ -5,6 +5,8 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "operands.h"
+
 namespace acemi {
 
 BlockRunner::BlockRunner() {
@@ -47,11 +49,12 @@ void BlockRunner::run(const BlockShape& sh, const std::vector<DevLayer>& layers,
     const int H = sh.hidden, D = sh.head_dim, I = sh.intermediate;
     ACEMI_CHECK(B >= 1 && n >= 1 && D == 128, "blocks: bad shape");
     ACEMI_CHECK(n_layers >= 0 && n_layers <= (int)layers.size(), "blocks: layer count");
-    const int64_t M = (int64_t)B * n;
+    const int M = (int)((int64_t)B * n);
     const int Npad = (int)round_up(n, 128);
-    const int qd = sh.hq * D, kd = sh.hkv * D;
-    const int64_t q_plane = (int64_t)B * sh.hq * Npad * D;
-    const int64_t k_plane = (int64_t)B * sh.hkv * Npad * D;
+    const AttnDims dims{B, sh.hq, sh.hkv, D, n, Npad, sh.eps};
+    const AttnPlanes planes{split_, pv_split_, false};
+    const int qd = dims.qd(), kd = dims.kd();
+    const int64_t q_plane = dims.q_plane(), k_plane = dims.k_plane();
     ACEMI_CHECK(x_.bytes >= (size_t)M * H * 4, "blocks: residual stream not initialised");
     ensure(act_, (size_t)M * std::max(H, qd) * 2);
     ensure(attn_, (size_t)M * qd * 2);
@@ -87,89 +90,24 @@ void BlockRunner::run(const BlockShape& sh, const std::vector<DevLayer>& layers,
     uint16_t* attn = get<uint16_t>(attn_);
     uint16_t* act2 = get<uint16_t>(act2_);
     float* qkv = get<float>(qkv_);
+    uint16_t *qh = get<uint16_t>(qh_), *kh = get<uint16_t>(kh_), *vt = get<uint16_t>(vt_);
     launch_key_bias(key_mask, B, n, 1, n, Npad, get<float>(kbias_), s);
-    const float scale = 1.0f / std::sqrt((float)D);
+    const float* kbias = key_mask ? get<float>(kbias_) : nullptr;  // padding keys are masked in-kernel
     for (int li = 0; li < n_layers; ++li) {
         const DevLayer& ly = layers[li];
-        launch_rmsnorm_mod(at, x, (int)M, H, ly.self_norm, nullptr, nullptr, 0, n, sh.eps, act, s);
-        {
-            GemmEpilogue g;
-            g.kind = EPI_STORE_F32;
-            g.c_f32 = qkv;
-            g.ldc = qd + 2 * kd;
-            launch_gemm(act, H, ly.w_qkv.view(), (int)M, qd + 2 * kd, H, g, s);
-        }
-        {
-            PrepArgs pa{};
-            pa.src = qkv;
-            pa.ld = qd + 2 * kd;
-            pa.q_col = 0;
-            pa.k_col = qd;
-            pa.v_col = qd + kd;
-            pa.hq = sh.hq;
-            pa.hkv = sh.hkv;
-            pa.n_tok = n;
-            pa.n_pad = Npad;
-            pa.B = B;
-            pa.q_norm = ly.sq_norm;
-            pa.k_norm = ly.sk_norm;
-            pa.rope_cos = get<float>(cos_);
-            pa.rope_sin = get<float>(sin_);
-            pa.eps = sh.eps;
-            pa.qh = get<uint16_t>(qh_);
-            pa.kh = get<uint16_t>(kh_);
-            pa.vt = get<uint16_t>(vt_);
-            pa.q_plane = split_ ? q_plane : 0;
-            pa.k_plane = split_ ? k_plane : 0;
-            pa.v_plane = pv_split_ ? k_plane : 0;
-            launch_attn_prep(pa, s);
-        }
-        {
-            AttnArgs aa{};
-            aa.q = get<uint16_t>(qh_);
-            aa.k = get<uint16_t>(kh_);
-            aa.vt = get<uint16_t>(vt_);
-            aa.kbias = key_mask ? get<float>(kbias_) : nullptr;  // padding keys are masked in-kernel
-            aa.out = attn;
-            aa.B = B;
-            aa.Hq = sh.hq;
-            aa.Hkv = sh.hkv;
-            aa.nq = n;
-            aa.nq_pad = Npad;
-            aa.nk = n;
-            aa.nk_pad = Npad;
-            aa.window = ly.sliding ? std::max(sh.sliding_window, 0) : 0;
-            aa.causal = causal;
-            aa.scale = scale;
-            aa.split = split_;
-            aa.pv_split = pv_split_;
-            aa.q_plane = q_plane;
-            aa.k_plane = k_plane;
-            aa.v_plane = k_plane;
-            launch_attention(at, aa, s);
-        }
-        {
-            GemmEpilogue g;  // h = x + o_proj(attn)
-            g.kind = EPI_RESID;
-            g.c_f32 = x;
-            g.ldc = H;
-            launch_gemm(attn, qd, ly.w_o.view(), (int)M, H, qd, g, s);
-        }
-        launch_rmsnorm_mod(at, x, (int)M, H, ly.mlp_norm, nullptr, nullptr, 0, n, sh.eps, act, s);
-        {
-            GemmEpilogue g;
-            g.kind = EPI_SWIGLU;
-            g.c_act = act2;
-            g.ldc = I;
-            launch_gemm(act, H, ly.w_gu.view(), (int)M, 2 * I, H, g, s);
-        }
-        {
-            GemmEpilogue g;  // x = h + down(act)
-            g.kind = EPI_RESID;
-            g.c_f32 = x;
-            g.ldc = H;
-            launch_gemm(act2, I, ly.w_down.view(), (int)M, H, I, g, s);
-        }
+        launch_rmsnorm_mod(at, x, M, H, ly.self_norm, nullptr, nullptr, 0, n, sh.eps, act, s);
+        launch_gemm(act, H, ly.w_qkv.view(), M, qd + 2 * kd, H, epi_store_f32(qkv, qd + 2 * kd), s);
+        launch_attn_prep(self_prep(dims, planes, qkv, qd + 2 * kd, ly.sq_norm, ly.sk_norm, get<float>(cos_),
+                                   get<float>(sin_), qh, kh, vt),
+                         s);
+        launch_attention(at,
+                         attn_args(dims, planes, qh, kh, vt, kbias, n, Npad, dims.k_plane(),
+                                   ly.sliding ? std::max(sh.sliding_window, 0) : 0, causal, nullptr, attn),
+                         s);
+        launch_gemm(attn, qd, ly.w_o.view(), M, H, qd, epi_resid(x, H), s);  // h = x + o_proj(attn)
+        launch_rmsnorm_mod(at, x, M, H, ly.mlp_norm, nullptr, nullptr, 0, n, sh.eps, act, s);
+        launch_gemm(act, H, ly.w_gu.view(), M, 2 * I, H, epi_swiglu(act2, I), s);
+        launch_gemm(act2, I, ly.w_down.view(), M, H, I, epi_resid(x, H), s);  // x = h + down(act)
     }
 }
 

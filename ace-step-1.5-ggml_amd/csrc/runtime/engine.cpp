@@ -2,11 +2,15 @@
 // (acestep_dit_model.cpp:1316-1560) as a fixed sequence of fused gfx950 kernels.
 #include "engine.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <type_traits>
+
+#include "operands.h"
 
 namespace acemi {
 
@@ -290,63 +294,118 @@ void DitEngine::rope_for(int Np, hipStream_t s) {
 }
 
 void DitEngine::forward(const ForwardIO& io, hipStream_t s) {
-    if (qact_) {
-        forward_qact(io, s);
-        return;
-    }
+    if (qact_)
+        walk<true>(io, s);
+    else
+        walk<false>(io, s);
+}
+
+// The one walk of the DiT graph.  QACT = false is the product: bf16 activation rows (Row = uint16_t) through
+// launch_gemm on the staged / imaged weights, attention at the engine's precision.  QACT = true is the
+// ggml-arithmetic parity mode (engine_qact.cpp): f32 rows in one buffer (every Row* below is qf_), each linear through
+// qlinear on the resident weights, attention at the f32 precision with f32 output.  The modes differ only in the
+// `if constexpr` arms and the five small lambdas below; everything else is one sequence.
+template <bool QACT>
+void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
+    using Row = std::conditional_t<QACT, float, uint16_t>;
     const DitModel& m = model_;
     const DitConfig& c = m.cfg;
     const ActType at = m.act;
     const int B = io.B, T = io.T, L = io.L > 0 ? io.L : 0;
     const int P = c.patch, H = c.hidden, I = c.intermediate, D = c.head_dim;
     const int Np = (T + P - 1) / P;
-    const int64_t M = (int64_t)B * Np;
+    const int M = (int)((int64_t)B * Np);
     const int Npad = (int)round_up(Np, 128);
     const int Lpad = (int)round_up(std::max(L, 1), 64);
-    const int qd = c.hq * D, kd = c.hkv * D;
-    const bool split = attn_split_;
-    const int64_t q_plane = (int64_t)B * c.hq * Npad * D;        // lo plane offsets (elements)
-    const int64_t k_plane = (int64_t)B * c.hkv * Npad * D;
-    const int64_t kc_plane = (int64_t)c.layers * B * c.hkv * Lpad * D;
+    const AttnDims dims{B, c.hq, c.hkv, D, Np, Npad, c.eps};
+    const AttnPlanes planes = QACT ? AttnPlanes{true, true, false} : AttnPlanes{attn_split_, attn_pv_split_, attn_f8_};
+    const int qd = dims.qd(), kd = dims.kd();
+    const int64_t kc_layer = (int64_t)B * c.hkv * Lpad * D;  // one layer's cross K (or V^T) plane
+    const int64_t kc_plane = c.layers * kc_layer;            // lo plane offset of kc_ / vc_
     ACEMI_CHECK(B >= 1 && B <= 8, "batch must be 1..8 per GPU");
     ACEMI_CHECK(T >= 1, "seq_len must be > 0");
     ACEMI_CHECK(L == 0 || io.enc != nullptr, "encoder_hidden_states required when enc_len > 0");
+    const int kin = m.proj_in_w.k_mult(), kout = m.proj_out_w.k_mult();
+    if constexpr (QACT)
+        ACEMI_CHECK(kin == 1 && kout == 1,
+                    "quantized-activation mode: F32 proj_in / proj_out (GGUF) are not supported");
     prepare_shape(B, Np, L);
     rope_for(Np, s);
     // bf16 images written by an earlier forward (possibly on another stream) are complete before this one reads them
     if (stage_ev_set_) ACEMI_HIP(hipStreamWaitEvent(s, stage_ev_, 0));
     images_written_ = false;
+    // parity: the cross K/V planes below are this mode's (f32 precision), not the cached ones
+    if constexpr (QACT) cross_key_.valid = false;
 
     int n_layers = c.layers;
     if (io.max_layers > 0) n_layers = std::min(n_layers, io.max_layers);
+    const int Kin = kin * P * c.in_channels;
 
-    uint16_t* a0 = get<uint16_t>(a0_);
     float* x = get<float>(x_);
-    uint16_t* act = get<uint16_t>(act_);
-    uint16_t* attn = get<uint16_t>(attn_);
-    uint16_t* act2 = get<uint16_t>(act2_);
-    float* qkv = get<float>(qkv_);
+    Row *a0, *act, *attn, *act2;  // packed input, norm output, attention output, SwiGLU output
+    float* attn_f32 = nullptr;
+    if constexpr (QACT) {
+        ensure(qf_, (size_t)M * std::max({H, qd, I, Kin}) * 4);
+        a0 = act = attn = act2 = attn_f32 = get<float>(qf_);
+    } else {
+        a0 = get<uint16_t>(a0_);
+        act = get<uint16_t>(act_);
+        attn = get<uint16_t>(attn_);
+        act2 = get<uint16_t>(act2_);
+    }
+
+    // ---- the seam
+    auto weight = [&](const DevWeight& w) { return QACT ? w.view() : dense_view(w, s); };
+    auto linear = [&](const Row* in, int ld, int rows, const WeightView& w, int N, int K, const GemmEpilogue& e,
+                      const char* name) {
+        if constexpr (QACT) {
+            qlinear(in, ld, rows, w, N, K, e, name, s);  // (times itself)
+        } else {
+            tic(s);
+            launch_gemm(in, ld, w, rows, N, K, e, s);
+            toc(name, s);
+        }
+    };
+    // a projection feeding attention, with the operand prep `pa` in its epilogue (product: qkv_gemm's choice)
+    auto project = [&](const WeightView& w, int N, const PrepArgs& pa, const char* name) {
+        if constexpr (QACT)
+            qlinear(act, H, M, w, N, H, epi_qkv_prep(pa), name, s);
+        else
+            qkv_gemm(act, w, M, N, pa, name, s);
+    };
+    auto norm = [&](ActType t, const float* w, const float* scale, const float* shift, int64_t stride, Row* out,
+                    bool x3) {
+        tic(s);
+        if constexpr (QACT)
+            launch_rmsnorm_mod_f32(x, M, H, w, scale, shift, stride, Np, c.eps, out, s);
+        else
+            launch_rmsnorm_mod(t, x, M, H, w, scale, shift, stride, Np, c.eps, out, s, x3);
+        toc("rmsnorm_mod", s);
+    };
+    auto attention = [&](const uint16_t* k, const uint16_t* vt, const float* kbias, int nk, int nk_pad,
+                         int64_t kv_plane, int window, const char* name) {
+        tic(s);
+        launch_attention(at,
+                         attn_args(dims, planes, get<uint16_t>(qh_), k, vt, kbias, nk, nk_pad, kv_plane, window, false,
+                                   get<float>(attn_part_), get<uint16_t>(attn_), attn_f32),
+                         s);
+        toc(name, s);
+    };
 
     // ---- input pack + proj_in (:1343-1382)
     tic(s);
-    const int kin = m.proj_in_w.k_mult();
-    launch_pack_input(m.proj_in_w.act(), io.hidden, io.context, B, T, Np, P, c.audio_dim, c.ctx_dim(), a0, s,
-                      kin == 3);
+    if constexpr (QACT)
+        launch_pack_input_f32(io.hidden, io.context, B, T, Np, P, c.audio_dim, c.ctx_dim(), a0, s);
+    else
+        launch_pack_input(m.proj_in_w.act(), io.hidden, io.context, B, T, Np, P, c.audio_dim, c.ctx_dim(), a0, s,
+                          kin == 3);
     toc("pack_input", s);
-    {
-        GemmEpilogue e;
-        e.kind = EPI_STORE_F32;
-        e.bias = m.proj_in_b;
-        e.c_f32 = x;
-        e.ldc = H;
-        tic(s);
-        launch_gemm(a0, kin * P * c.in_channels, dense_view(m.proj_in_w, s), (int)M, H, kin * P * c.in_channels, e, s);
-        toc("gemm_proj_in", s);
-    }
+    linear(a0, Kin, M, weight(m.proj_in_w), H, Kin, epi_store_f32(x, H, m.proj_in_b), "gemm_proj_in");
 
-    // ---- timestep embeddings (:1416-1424, timestep_forward :1286-1308), or the sampler's precomputed rows
+    // ---- timestep embeddings (:1416-1424, timestep_forward :1286-1308), or the sampler's precomputed rows, and the
+    // key masks.  Parity leaves both out of the profile: its timestep linears time themselves (tic / toc do not nest)
     {
-        tic(s);
+        if constexpr (!QACT) tic(s);
         const float* proj = io.ts_proj;
         const float* temb_t = io.ts_temb_t;
         const float* temb_r = io.ts_temb_r;
@@ -358,94 +417,63 @@ void DitEngine::forward(const ForwardIO& io, hipStream_t s) {
         }
         launch_layer_mods(m.tables, proj, n_layers, B, H, get<float>(mods_), s);
         launch_out_mods(m.out_table, temb_t, temb_r, B, H, get<float>(outmod_), s);
-        toc("timestep", s);
+        if constexpr (!QACT) {
+            toc("timestep", s);
+            tic(s);
+        }
+        launch_key_bias(io.mask, B, T, P, Np, Npad, get<float>(kbias_), s);
+        if (L > 0) launch_key_bias(io.enc_mask, B, L, 1, L, Lpad, get<float>(kbias_c_), s);
+        if constexpr (!QACT) toc("key_bias", s);
     }
 
-    // ---- key masks
-    tic(s);
-    launch_key_bias(io.mask, B, T, P, Np, Npad, get<float>(kbias_), s);
-    if (L > 0) launch_key_bias(io.enc_mask, B, L, 1, L, Lpad, get<float>(kbias_c_), s);
-    toc("key_bias", s);
-
-    // ---- condition embedder (:1384-1414) + per-layer cross K/V (constant over the layer loop)
-    const bool reuse = io.reuse_cross && cross_key_.valid && cross_key_.B == B && cross_key_.L == L &&
+    // ---- condition embedder (:1384-1414) + per-layer cross K/V (constant over the layer loop; the product reuses
+    // the previous forward's on request)
+    const bool reuse = !QACT && io.reuse_cross && cross_key_.valid && cross_key_.B == B && cross_key_.L == L &&
                        cross_key_.layers >= n_layers && cross_key_.enc == io.enc;
     if (L > 0 && !reuse) {
-        cross_key_ = CrossKey{true, B, L, n_layers, io.enc};
-        const int64_t Me = (int64_t)B * L;
-        uint16_t* enc_act = get<uint16_t>(enc_act_);
-        uint16_t* encp = get<uint16_t>(encp_);
-        tic(s);
-        launch_to_act(at, io.enc, Me * H, false, enc_act, s);
-        GemmEpilogue e;
-        e.kind = EPI_STORE_ACT;
-        e.bias = m.cond_b;
-        e.c_act = encp;
-        e.ldc = H;
-        launch_gemm(enc_act, H, dense_view(m.cond_w, s), (int)Me, H, H, e, s);
-        toc("gemm_condition", s);
-        // one GEMM for every layer's cross k|v when the weights are fused: ckv [Me][n_layers*2kd]
-        const bool fused = m.w_ckv_all.q != nullptr;
-        const int ld_ckv = fused ? n_layers * 2 * kd : 2 * kd;
-        if (fused) {
-            GemmEpilogue ek;
-            ek.kind = EPI_STORE_F32;
-            ek.c_f32 = get<float>(ckv_);
-            ek.ldc = ld_ckv;
+        const int Me = (int)((int64_t)B * L);
+        Row* encp;
+        if constexpr (QACT) {
+            ensure(encf_, (size_t)Me * H * 4);
+            encp = get<float>(encf_);
+            qlinear(io.enc, H, Me, m.cond_w.view(), H, H, epi_store_f32(encp, H, m.cond_b), "gemm_condition", s);
+        } else {
+            cross_key_ = CrossKey{true, B, L, n_layers, io.enc};
+            encp = get<uint16_t>(encp_);
             tic(s);
-            launch_gemm(encp, H, dense_view(m.w_ckv_all, s), (int)Me, ld_ckv, H, ek, s);  // first n_layers layers
-            toc("gemm_cross_kv", s);
+            launch_to_act(at, io.enc, (int64_t)Me * H, false, get<uint16_t>(enc_act_), s);
+            launch_gemm(get<uint16_t>(enc_act_), H, dense_view(m.cond_w, s), Me, H, H, epi_store_act(encp, H, m.cond_b),
+                        s);
+            toc("gemm_condition", s);
         }
+        // one GEMM for every layer's cross k|v when the weights are fused: ckv [Me][n_layers*2kd]; the product then
+        // re-lays all of them out in one launch too, parity runs one prep per layer
+        const bool fused = m.w_ckv_all.q != nullptr;
+        const bool one_prep = fused && !QACT;
+        const int ld_ckv = fused ? n_layers * 2 * kd : 2 * kd;
+        float* ckv = get<float>(ckv_);
         for (int li = 0; li < n_layers; ++li) {
             const DevLayer& ly = m.layers[li];
-            if (!fused) {
-                GemmEpilogue ek;
-                ek.kind = EPI_STORE_F32;
-                ek.c_f32 = get<float>(ckv_);
-                ek.ldc = 2 * kd;
-                tic(s);
-                launch_gemm(encp, H, dense_view(ly.w_ckv, s), (int)Me, 2 * kd, H, ek, s);
-                toc("gemm_cross_kv", s);
-            }
-            PrepArgs pa{};
-            pa.src = get<float>(ckv_) + (fused ? (size_t)li * 2 * kd : 0);
-            pa.ld = ld_ckv;
-            pa.q_col = -1;
-            pa.k_col = 0;
-            pa.v_col = kd;
-            pa.hq = c.hq;
-            pa.hkv = c.hkv;
-            pa.n_tok = L;
-            pa.n_pad = Lpad;
-            pa.B = B;
-            pa.k_norm = ly.ck_norm;
-            pa.eps = c.eps;
-            pa.kh = get<uint16_t>(kc_) + (size_t)li * B * c.hkv * Lpad * D;
-            pa.vt = get<uint16_t>(vc_) + (size_t)li * B * c.hkv * D * Lpad;
-            pa.k_plane = split ? kc_plane : 0;
-            pa.v_plane = attn_pv_split_ ? kc_plane : 0;
-            pa.f8 = attn_f8_ ? 1 : 0;
-            if (fused) {  // every layer's cross K/V re-layout in one launch (PrepArgs::layers)
-                pa.layers = n_layers;
-                pa.src_layer = 2 * kd;
-                pa.kh_layer = (int64_t)B * c.hkv * Lpad * D;
-                pa.vt_layer = (int64_t)B * c.hkv * D * Lpad;
-                pa.k_norm_layers = cross_norm_table();
-            }
+            if (li == 0 || !fused)  // (fused: the first n_layers layers)
+                linear(encp, H, Me, weight(fused ? m.w_ckv_all : ly.w_ckv), ld_ckv, H, epi_store_f32(ckv, ld_ckv),
+                       "gemm_cross_kv");
             tic(s);
-            launch_attn_prep(pa, s);
+            launch_attn_prep(cross_kv_prep(dims, planes, L, Lpad, ckv + (fused ? (size_t)li * 2 * kd : 0), ld_ckv,
+                                           ly.ck_norm, get<uint16_t>(kc_) + li * kc_layer,
+                                           get<uint16_t>(vc_) + li * kc_layer, kc_plane, n_layers,
+                                           one_prep ? cross_norm_table() : nullptr),
+                             s);
             toc("attn_prep", s);
-            if (fused) break;
+            if (one_prep) break;
         }
     }
 
     const float* mods = get<float>(mods_);
     const int64_t mstride = 6LL * H;  // per item within a layer
-    const float scale = 1.0f / std::sqrt((float)D);
 
-    // staged dequant: each layer's quantized block matrices are expanded to their bf16 image right before the
-    // layer, in stream order, into one workspace slot (see engine.h)
-    const bool staged = staged_quant_ && n_layers > 0 && weight_quantized(m.layers[0].w_gu.fmt);
+    // staged dequant (product): each layer's quantized block matrices are expanded to their bf16 image right before
+    // the layer, in stream order, into one workspace slot (see engine.h)
+    const bool staged = !QACT && staged_quant_ && n_layers > 0 && weight_quantized(m.layers[0].w_gu.fmt);
     bool restage = true;
     if (staged) {
         const DevLayer& l0 = m.layers[0];
@@ -463,8 +491,9 @@ void DitEngine::forward(const ForwardIO& io, hipStream_t s) {
     for (int li = 0; li < n_layers; ++li) {  // :1466-1535
         const DevLayer& ly = m.layers[li];
         if (staged && restage) stage_layer(li, s);
-        if (prefetch_blocks_ > 0 && li + 1 < n_layers && !(staged && restage)) prefetch_layer(li + 1, staged, s);
-        const LayerViews lw = layer_views(li, staged);
+        if (!QACT && prefetch_blocks_ > 0 && li + 1 < n_layers && !(staged && restage))
+            prefetch_layer(li + 1, staged, s);
+        const LayerViews lw = layer_views(li, staged);  // (not staged: the resident weights)
         const float* lm = mods + (size_t)li * B * 6 * H;
         const float* shift_msa = lm + 0 * H;
         const float* scale_msa = lm + 1 * H;
@@ -473,189 +502,41 @@ void DitEngine::forward(const ForwardIO& io, hipStream_t s) {
         const float* c_scale = lm + 4 * H;
         const float* c_gate = lm + 5 * H;
 
-        // self-attention block
-        tic(s);
-        launch_rmsnorm_mod(at, x, (int)M, H, ly.self_norm, scale_msa, shift_msa, mstride, Np, c.eps, act, s);
-        toc("rmsnorm_mod", s);
-        {
-            // QKV projection with QK-RMSNorm, RoPE and the attention re-layout fused into its epilogue
-            // (EPI_QKV_PREP; ACE_MI_UNFUSED_PREP=1 runs the f32 store + attn_prep pair instead)
-            PrepArgs pa{};
-            pa.q_col = 0;
-            pa.k_col = qd;
-            pa.v_col = qd + kd;
-            pa.hq = c.hq;
-            pa.hkv = c.hkv;
-            pa.n_tok = Np;
-            pa.n_pad = Npad;
-            pa.B = B;
-            pa.q_norm = ly.sq_norm;
-            pa.k_norm = ly.sk_norm;
-            pa.rope_cos = get<float>(cos_);
-            pa.rope_sin = get<float>(sin_);
-            pa.eps = c.eps;
-            pa.qh = get<uint16_t>(qh_);
-            pa.kh = get<uint16_t>(kh_);
-            pa.vt = get<uint16_t>(vt_);
-            pa.q_plane = split ? q_plane : 0;
-            pa.k_plane = split ? k_plane : 0;
-            pa.v_plane = attn_pv_split_ ? k_plane : 0;
-            pa.f8 = attn_f8_ ? 1 : 0;
-            qkv_gemm(act, lw.qkv, (int)M, qd + 2 * kd, pa, qkv, "gemm_qkv", s);
-        }
-        {
-            AttnArgs aa{};
-            aa.q = get<uint16_t>(qh_);
-            aa.k = get<uint16_t>(kh_);
-            aa.vt = get<uint16_t>(vt_);
-            aa.kbias = io.mask ? get<float>(kbias_) : nullptr;  // padding keys are masked in-kernel
-            aa.part = get<float>(attn_part_);
-            aa.out = attn;
-            aa.B = B;
-            aa.Hq = c.hq;
-            aa.Hkv = c.hkv;
-            aa.nq = Np;
-            aa.nq_pad = Npad;
-            aa.nk = Np;
-            aa.nk_pad = Npad;
-            aa.window = ly.sliding ? std::max(c.sliding_window, 0) : 0;
-            if (ly.sliding && c.sliding_window <= 0) aa.window = 0;
-            aa.scale = scale;
-            aa.split = split;
-            aa.pv_split = attn_pv_split_;
-            aa.f8 = attn_f8_;
-            aa.q_plane = q_plane;
-            aa.k_plane = k_plane;
-            aa.v_plane = k_plane;
-            tic(s);
-            launch_attention(at, aa, s);
-            toc(ly.sliding ? "attn_self_sliding" : "attn_self_full", s);
-        }
-        {
-            GemmEpilogue e;
-            e.kind = EPI_RESID_GATED;
-            e.c_f32 = x;
-            e.ldc = H;
-            e.gate = gate_msa;
-            e.gate_stride = mstride;
-            e.rows_per_item = Np;
-            tic(s);
-            if (li == fault_.layer) {  // (the injected fault must reach the norm that follows)
-                launch_gemm(attn, qd, lw.o, (int)M, H, qd, e, s);
-                launch_fault_tile(x, H, (int)M, fault_.row, fault_.col, fault_.amp, s);
-            } else {
-                launch_gemm(attn, qd, lw.o, (int)M, H, qd, e, s);
-            }
-            toc("gemm_o", s);
-        }
+        // self-attention block: the QKV projection with QK-RMSNorm, RoPE and the attention re-layout in its epilogue
+        norm(at, ly.self_norm, scale_msa, shift_msa, mstride, act, false);
+        project(lw.qkv, qd + 2 * kd,
+                self_prep(dims, planes, nullptr, 0, ly.sq_norm, ly.sk_norm, get<float>(cos_), get<float>(sin_),
+                          get<uint16_t>(qh_), get<uint16_t>(kh_), get<uint16_t>(vt_)),
+                "gemm_qkv");
+        attention(get<uint16_t>(kh_), get<uint16_t>(vt_), io.mask ? get<float>(kbias_) : nullptr, Np, Npad,
+                  dims.k_plane(), ly.sliding ? std::max(c.sliding_window, 0) : 0,  // padding keys: masked in-kernel
+                  ly.sliding ? "attn_self_sliding" : "attn_self_full");
+        linear(attn, qd, M, lw.o, H, qd, epi_resid_gated(x, H, gate_msa, mstride, Np), "gemm_o");
+        if (!QACT && li == fault_.layer)  // TEST ONLY: the injected fault must reach the norm that follows
+            launch_fault_tile(x, H, M, fault_.row, fault_.col, fault_.amp, s);
 
         // cross-attention block (:1502-1520): no AdaLN, no gate, no RoPE
         if (ly.cross && L > 0) {
-            tic(s);
-            launch_rmsnorm_mod(at, x, (int)M, H, ly.cross_norm, nullptr, nullptr, 0, Np, c.eps, act, s);
-            toc("rmsnorm_mod", s);
-            {
-                PrepArgs pa{};
-                pa.q_col = 0;
-                pa.k_col = -1;
-                pa.v_col = -1;
-                pa.hq = c.hq;
-                pa.hkv = c.hkv;
-                pa.n_tok = Np;
-                pa.n_pad = Npad;
-                pa.B = B;
-                pa.q_norm = ly.cq_norm;
-                pa.eps = c.eps;
-                pa.qh = get<uint16_t>(qh_);
-                pa.q_plane = split ? q_plane : 0;
-                pa.f8 = attn_f8_ ? 1 : 0;
-                qkv_gemm(act, lw.cq, (int)M, qd, pa, qkv, "gemm_cross_q", s);
-            }
-            {
-                AttnArgs aa{};
-                aa.q = get<uint16_t>(qh_);
-                aa.k = get<uint16_t>(kc_) + (size_t)li * B * c.hkv * Lpad * D;
-                aa.vt = get<uint16_t>(vc_) + (size_t)li * B * c.hkv * D * Lpad;
-                aa.kbias = io.enc_mask ? get<float>(kbias_c_) : nullptr;
-                aa.part = get<float>(attn_part_);
-                aa.out = attn;
-                aa.B = B;
-                aa.Hq = c.hq;
-                aa.Hkv = c.hkv;
-                aa.nq = Np;
-                aa.nq_pad = Npad;
-                aa.nk = L;
-                aa.nk_pad = Lpad;
-                aa.window = 0;
-                aa.scale = scale;
-                aa.split = split;
-                aa.pv_split = attn_pv_split_;
-            aa.f8 = attn_f8_;
-                aa.q_plane = q_plane;
-                aa.k_plane = kc_plane;
-                aa.v_plane = kc_plane;
-                tic(s);
-                launch_attention(at, aa, s);
-                toc("attn_cross", s);
-            }
-            {
-                GemmEpilogue e;
-                e.kind = EPI_RESID;
-                e.c_f32 = x;
-                e.ldc = H;
-                tic(s);
-                launch_gemm(attn, qd, lw.co, (int)M, H, qd, e, s);
-                toc("gemm_cross_o", s);
-            }
+            norm(at, ly.cross_norm, nullptr, nullptr, 0, act, false);
+            project(lw.cq, qd, cross_q_prep(dims, planes, ly.cq_norm, get<uint16_t>(qh_)), "gemm_cross_q");
+            attention(get<uint16_t>(kc_) + li * kc_layer, get<uint16_t>(vc_) + li * kc_layer,
+                      io.enc_mask ? get<float>(kbias_c_) : nullptr, L, Lpad, kc_plane, 0, "attn_cross");
+            linear(attn, qd, M, lw.co, H, qd, epi_resid(x, H), "gemm_cross_o");
         }
 
-        // MLP block (:1522-1534)
-        tic(s);
-        launch_rmsnorm_mod(at, x, (int)M, H, ly.mlp_norm, c_scale, c_shift, mstride, Np, c.eps, act, s);
-        toc("rmsnorm_mod", s);
-        {
-            GemmEpilogue e;
-            e.kind = EPI_SWIGLU;
-            e.c_act = act2;
-            e.ldc = I;
-            tic(s);
-            launch_gemm(act, H, lw.gu, (int)M, 2 * I, H, e, s);
-            toc("gemm_gate_up", s);
-        }
-        {
-            GemmEpilogue e;
-            e.kind = EPI_RESID_GATED;
-            e.c_f32 = x;
-            e.ldc = H;
-            e.gate = c_gate;
-            e.gate_stride = mstride;
-            e.rows_per_item = Np;
-            tic(s);
-            launch_gemm(act2, I, lw.down, (int)M, H, I, e, s);
-            toc("gemm_down", s);
-        }
+        // MLP block (:1522-1534); parity's SwiGLU rows overwrite their own (already quantized) input
+        norm(at, ly.mlp_norm, c_scale, c_shift, mstride, act, false);
+        linear(act, H, M, lw.gu, 2 * I, H, epi_swiglu(act2, I), "gemm_gate_up");
+        linear(act2, I, M, lw.down, H, I, epi_resid_gated(x, H, c_gate, mstride, Np), "gemm_down");
     }
 
     // ---- output head (:1537-1559)
     {
         const float* om = get<float>(outmod_);
-        const int kout = m.proj_out_w.k_mult();
-        uint16_t* head_in = kout == 3 ? get<uint16_t>(act2_) : act;  // act2_ is sized for M x 3H too
-        tic(s);
-        launch_rmsnorm_mod(m.proj_out_w.act(), x, (int)M, H, m.norm_out, om + H, om, 2LL * H, Np, c.eps, head_in,
-                           s, kout == 3);
-        toc("rmsnorm_mod", s);
-        GemmEpilogue e;
-        e.kind = EPI_PROJ_OUT;
-        e.bias = m.proj_out_b;
-        e.c_f32 = io.out;
-        e.rows_per_item = Np;
-        e.out_T = T;
-        e.out_ch = c.audio_dim;
-        e.patch = P;
-        tic(s);
-        launch_gemm(head_in, kout * H, dense_view(m.proj_out_w, s), (int)M, P * c.audio_dim, kout * H, e, s);
-        toc("gemm_proj_out", s);
+        Row* head_in = kout == 3 ? act2 : act;  // act2_ is sized for M x 3H too
+        norm(m.proj_out_w.act(), m.norm_out, om + H, om, 2LL * H, head_in, kout == 3);
+        linear(head_in, kout * H, M, weight(m.proj_out_w), P * c.audio_dim, kout * H,
+               epi_proj_out(io.out, m.proj_out_b, Np, T, c.audio_dim, P), "gemm_proj_out");
     }
     if (images_written_) {
         if (!stage_ev_) ACEMI_HIP(hipEventCreateWithFlags(&stage_ev_, hipEventDisableTiming));
@@ -708,31 +589,20 @@ DitEngine::TimestepRows DitEngine::precompute_timesteps(const float* t, const fl
     return TimestepRows{get<float>(ts_proj_), get<float>(ts_temb_t_), get<float>(ts_temb_r_)};
 }
 
-// A projection feeding attention: with EPI_QKV_PREP the GEMM epilogue writes the attention operands of
-// `pa` directly; the unfused path (ACE_MI_UNFUSED_PREP=1, A/B and debugging) stores f32 to `scratch`
+// A projection of the product walk feeding attention: with EPI_QKV_PREP the GEMM epilogue writes the attention
+// operands of `prep` directly; the unfused path (ACE_MI_UNFUSED_PREP=1, A/B and debugging) stores f32 to qkv_
 // and runs attn_prep over it.
-void DitEngine::qkv_gemm(const uint16_t* act, const WeightView& w, int M, int N, PrepArgs pa, float* scratch,
-                         const char* name, hipStream_t s) {
+void DitEngine::qkv_gemm(const uint16_t* act, const WeightView& w, int M, int N, PrepArgs prep, const char* name,
+                         hipStream_t s) {
     const int H = model_.cfg.hidden;
-    GemmEpilogue e;
-    if (fused_prep_) {
-        e.kind = EPI_QKV_PREP;
-        e.prep = pa;
-        tic(s);
-        launch_gemm(act, H, w, M, N, H, e, s);
-        toc(name, s);
-        return;
-    }
-    e.kind = EPI_STORE_F32;
-    e.c_f32 = scratch;
-    e.ldc = N;
+    prep.src = fused_prep_ ? nullptr : get<float>(qkv_);
+    prep.ld = fused_prep_ ? 0 : N;
     tic(s);
-    launch_gemm(act, H, w, M, N, H, e, s);
+    launch_gemm(act, H, w, M, N, H, fused_prep_ ? epi_qkv_prep(prep) : epi_store_f32(get<float>(qkv_), N), s);
     toc(name, s);
-    pa.src = scratch;
-    pa.ld = N;
+    if (fused_prep_) return;
     tic(s);
-    launch_attn_prep(pa, s);
+    launch_attn_prep(prep, s);
     toc("attn_prep", s);
 }
 
@@ -749,10 +619,7 @@ void DitEngine::encode(const EncodeIO& io, hipStream_t s) {
     ensure(ein_, (size_t)M * in_dim * 2);
     uint16_t* ein = get<uint16_t>(ein_);
     launch_to_act(io.proj->act(), io.in, M * in_dim, false, ein, s);
-    GemmEpilogue pe;
-    pe.kind = EPI_STORE_F32;
-    pe.bias = io.proj_b;
-    pe.ldc = H;
+    GemmEpilogue pe = epi_store_f32(nullptr, H, io.proj_b);
     if (!io.enc) {  // projection only (the text projector)
         ACEMI_CHECK(!io.first_only, "encoder: first_only needs an encoder");
         pe.c_f32 = io.out;
@@ -785,26 +652,17 @@ void DitEngine::probe_gemm(int which, int M, int iters, hipStream_t s) {
     prepare_shape(1, M, 0);
     const DevLayer& ly = m.layers[0];
     for (int it = 0; it < iters; ++it) {
-        GemmEpilogue e;
+        tic(s);
         if (which == 0) {
-            e.kind = EPI_SWIGLU;
-            e.c_act = get<uint16_t>(act2_);
-            e.ldc = I;
-            tic(s);
-            launch_gemm(get<uint16_t>(act_), H, ly.w_gu.view(), M, 2 * I, H, e, s);
+            launch_gemm(get<uint16_t>(act_), H, ly.w_gu.view(), M, 2 * I, H, epi_swiglu(get<uint16_t>(act2_), I), s);
             toc("probe_gemm_gate_up", s);
         } else {
-            e.kind = EPI_RESID_GATED;
-            e.c_f32 = get<float>(x_);
-            e.ldc = H;
-            e.gate = get<float>(mods_);
-            e.gate_stride = 0;
-            e.rows_per_item = M;
-            tic(s);
-            launch_gemm(get<uint16_t>(act2_), I, ly.w_down.view(), M, H, I, e, s);
+            launch_gemm(get<uint16_t>(act2_), I, ly.w_down.view(), M, H, I,
+                        epi_resid_gated(get<float>(x_), H, get<float>(mods_), 0, M), s);
             toc("probe_gemm_down", s);
         }
     }
 }
 
 }  // namespace acemi
+

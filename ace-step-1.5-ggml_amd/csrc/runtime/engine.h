@@ -140,9 +140,13 @@ class DitEngine {
     bool attn_pv_split_ = false;  // hi/lo fp16 P.V operands too
     bool attn_f8_ = false;        // f8c: the lo planes hold fp8 operands (AttnArgs::f8)
     bool fused_prep_ = true;      // EPI_QKV_PREP (ACE_MI_UNFUSED_PREP=1: f32 store + attn_prep)
-    void qkv_gemm(const uint16_t* act, const WeightView& w, int M, int N, PrepArgs pa, float* scratch,
-                  const char* name, hipStream_t s);
-    // ggml-faithful quantized-activation mode (ACE_MI_QUANT_ACT=q8, runtime/engine_qact.cpp): every linear with a
+    void qkv_gemm(const uint16_t* act, const WeightView& w, int M, int N, PrepArgs prep, const char* name,
+                  hipStream_t s);
+    // forward(): the one walk of the graph, product (QACT = false) or quantized-activation parity mode (engine.cpp)
+    template <bool QACT>
+    void walk(const ForwardIO& io, hipStream_t s);
+    // ggml-faithful quantized-activation mode (ACE_MI_QUANT_ACT=q8, walk<true> with runtime/engine_qact.cpp's
+    // arithmetic): every linear with a
     // block-format weight quantizes its f32 input rows to Q8_0 / Q8_K blocks and runs the integer-dot GEMM
     // (launch_gemm_a8), the activations between the linears stay f32 (RMSNorm, attention output, SwiGLU), and
     // attention runs at the f32 precision -- the arithmetic of the reference's ggml graph.  A parity mode: the
@@ -152,7 +156,6 @@ class DitEngine {
     Buf qa16_;                      // Q8_0 activation blocks as bf16(q) rows (the bf16-MFMA form, gemm_a8_bf16_path)
     std::map<const void*, Buf> q8img_;  // bf16(q) image of each Q8_0 plane, made at its first q8-mode use
     const uint16_t* q8_image(const WeightView& w, int N, int K, hipStream_t s);
-    void forward_qact(const ForwardIO& io, hipStream_t s);
     void qlinear(const float* x, int64_t ldx, int M, const WeightView& w, int N, int K, const GemmEpilogue& e,
                  const char* name, hipStream_t s, bool silu_in = false);
     void timestep_embed_qact(const float* t, const float* r, int rows, float* proj, float* temb_t, float* temb_r,

@@ -127,7 +127,7 @@ struct DitModel {
     ~DitModel();
 };
 
-// ACE_MI_QUANT_ACT=q8: the ggml-faithful quantized-activation mode (DitEngine::forward_qact); anything else (the
+// ACE_MI_QUANT_ACT=q8: the ggml-faithful quantized-activation mode (DitEngine::walk<true>); anything else (the
 // default, "bf16") = the product arithmetic, bf16 activations x bf16(dequant(W))
 bool quant_act_from_env();
 

@@ -81,7 +81,7 @@ def test_dit_forward_online_quantized(host_lib, tiny_ckpt, monkeypatch, qtype):
 
 @pytest.mark.parametrize("qtype", ["q8_0", "q4_k", "q6_k"])
 def test_dit_forward_quant_act_ggml_semantics(host_lib, tiny_ckpt, monkeypatch, qtype):
-    """ACE_MI_QUANT_ACT=q8 (DitEngine::forward_qact): f32 activations quantized to Q8_0 / Q8_K blocks before every
+    """ACE_MI_QUANT_ACT=q8 (the QACT arm of DitEngine::walk): f32 activations quantized to Q8_0 / Q8_K blocks before every
     quantized linear, against the oracle's ggml semantics (no engine_view) -- the orchestration of the mode, with
     the host restatement of its kernels; the sampler entry's precomputed timestep rows take the same path."""
     from oracle.dit_oracle import DitWeights, forward_with_floor
