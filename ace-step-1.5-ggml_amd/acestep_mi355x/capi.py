@@ -32,7 +32,8 @@ EXPORTED_SYMBOLS = (
     "ace_mi_create_on_device", "ace_mi_dit_get_info", "ace_mi_dit_forward_batched", "ace_mi_dit_sample",
     "ace_mi_dit_sample_ex",
     "ace_mi_profile_enable", "ace_mi_dit_set_attn_precision", "ace_mi_profile_reset", "ace_mi_profile_get", "ace_mi_probe_gemm",
-    "ace_mi_synchronize",
+    "ace_mi_synchronize", "ace_mi_dit_load_lora", "ace_mi_dit_set_lora_scale", "ace_mi_dit_unload_lora",
+    "ace_mi_dit_lora_info",
     "ace_mi_gemm_variant", "ace_ggml_load_vae", "ace_ggml_vae_get_info", "ace_ggml_vae_decode",
     "ace_mi_vae_out_len", "ace_mi_vae_decode_device", "ace_ggml_vae_encode", "ace_mi_vae_enc_out_len",
     "ace_mi_vae_encode_device", "ace_mi_quantize", "ace_mi_dequantize",
@@ -47,7 +48,7 @@ EXPORTED_SYMBOLS = (
 # product objects + the kernel self-test / micro-benchmark entries); the product library does not export them.
 SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_bench_attention", "ace_mi_bench_gemm",
                     "ace_mi_kernel_gemm_q", "ace_mi_kernel_dequant", "ace_mi_bench_gemm_q", "ace_mi_kernel_gemm_a8",
-                    "ace_mi_kernel_gemm_a8_mode", "ace_mi_kernel_attn_kh")
+                    "ace_mi_kernel_gemm_a8_mode", "ace_mi_kernel_attn_kh", "ace_mi_kernel_lora_merge")
 
 # qtype codes of ace_mi_quantize & co. (names as parse_quant_type, acestep_dit_model.cpp:27-37)
 QTYPES = {"q8_0": 1, "q4_k": 2, "q6_k": 3}
@@ -72,6 +73,19 @@ class AceMiCondInfo(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in (
         "hidden_size", "lyric_in_dim", "timbre_in_dim", "text_projector_in", "has_lyric_encoder", "lyric_layers",
         "has_timbre_encoder", "timbre_layers")]
+
+
+class AceMiLoraInfo(ctypes.Structure):
+    _fields_ = [("loaded", ctypes.c_int32), ("scale", ctypes.c_float), ("lora_alpha", ctypes.c_float),
+                ("min_rank", ctypes.c_int32), ("max_rank", ctypes.c_int32), ("num_modules", ctypes.c_int32),
+                ("num_images", ctypes.c_int32), ("image_bytes", ctypes.c_int64), ("merge_ms", ctypes.c_double)]
+
+
+class AceMiLoraJob(ctypes.Structure):
+    _fields_ = [("row0", ctypes.c_int32), ("rows", ctypes.c_int32), ("r", ctypes.c_int32), ("rows_mod", ctypes.c_int32),
+                ("A", ctypes.POINTER(ctypes.c_float)), ("B", ctypes.POINTER(ctypes.c_float)), ("eff", ctypes.c_float),
+                ("map", ctypes.c_int32), ("row_off", ctypes.c_int32), ("half", ctypes.c_int32),
+                ("copy_rest", ctypes.c_int32)]
 
 
 _LIB = None
@@ -129,6 +143,14 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ace_mi_probe_gemm.restype = ctypes.c_int
     lib.ace_mi_synchronize.argtypes = [vp]
     lib.ace_mi_synchronize.restype = ctypes.c_int
+    lib.ace_mi_dit_load_lora.argtypes = [vp, ctypes.c_char_p, f32]
+    lib.ace_mi_dit_load_lora.restype = ctypes.c_int
+    lib.ace_mi_dit_set_lora_scale.argtypes = [vp, f32]
+    lib.ace_mi_dit_set_lora_scale.restype = ctypes.c_int
+    lib.ace_mi_dit_unload_lora.argtypes = [vp]
+    lib.ace_mi_dit_unload_lora.restype = ctypes.c_int
+    lib.ace_mi_dit_lora_info.argtypes = [vp, ctypes.POINTER(AceMiLoraInfo)]
+    lib.ace_mi_dit_lora_info.restype = ctypes.c_int
     lib.ace_mi_gemm_variant.argtypes = [i32]
     lib.ace_mi_gemm_variant.restype = ctypes.c_int
     i64, u8p = ctypes.c_int64, ctypes.POINTER(ctypes.c_uint8)
@@ -233,6 +255,8 @@ def load_selftest_library() -> ctypes.CDLL:
     lib.ace_mi_kernel_gemm_a8_mode.restype = ctypes.c_int
     lib.ace_mi_kernel_attn_kh.argtypes = [i32]
     lib.ace_mi_kernel_attn_kh.restype = ctypes.c_int
+    lib.ace_mi_kernel_lora_merge.argtypes = [i32, i32, i32, i32, i32, u16p, u16p, ctypes.POINTER(AceMiLoraJob), i32]
+    lib.ace_mi_kernel_lora_merge.restype = ctypes.c_int
     _SELFTEST = lib
     return lib
 
@@ -533,6 +557,27 @@ class GGMLCAPIBridge:
                                            1 if cache_cross else 0, stream or None)
         self._ensure_ok(st, "ace_mi_dit_sample_ex")
 
+    # -- PEFT LoRA adapters (include/acestep_mi355x.h) -----------------------------------------------
+    def load_lora(self, path, scale: float = 1.0) -> None:
+        """Load adapter_config.json + adapter_model.safetensors of `path` at strength `scale` (replaces any
+        previous adapter; synchronous)."""
+        st = self.lib.ace_mi_dit_load_lora(self.ctx, str(path).encode("utf-8"), float(scale))
+        self._ensure_ok(st, "ace_mi_dit_load_lora")
+
+    def set_lora_scale(self, scale: float) -> None:
+        """Rebuild the adapted weights from the base at a new strength (0 = base weights, adapter kept)."""
+        self._ensure_ok(self.lib.ace_mi_dit_set_lora_scale(self.ctx, float(scale)), "ace_mi_dit_set_lora_scale")
+
+    def unload_lora(self) -> None:
+        self._ensure_ok(self.lib.ace_mi_dit_unload_lora(self.ctx), "ace_mi_dit_unload_lora")
+
+    def lora_info(self) -> dict:
+        info = AceMiLoraInfo()
+        self._ensure_ok(self.lib.ace_mi_dit_lora_info(self.ctx, ctypes.byref(info)), "ace_mi_dit_lora_info")
+        return dict(loaded=bool(info.loaded), scale=float(info.scale), lora_alpha=float(info.lora_alpha),
+                    min_rank=int(info.min_rank), max_rank=int(info.max_rank), num_modules=int(info.num_modules),
+                    num_images=int(info.num_images), image_bytes=int(info.image_bytes), merge_ms=float(info.merge_ms))
+
     def synchronize(self) -> None:
         self._ensure_ok(self.lib.ace_mi_synchronize(self.ctx), "ace_mi_synchronize")
 
@@ -680,6 +725,39 @@ def kernel_dequant(w_blocks: np.ndarray, qtype: str) -> np.ndarray:
                                    out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)))
     if st != ACE_GGML_OK:
         raise RuntimeError(f"ace_mi_kernel_dequant failed (status={st})")
+    return out
+
+
+LORA_ROWS_PLAIN, LORA_ROWS_INTERLEAVE = 0, 1
+
+
+def kernel_lora_merge(base_bits: Optional[np.ndarray], out_bits: np.ndarray, cols: int, jobs, fmt: str = "bf16",
+                      lib=None) -> np.ndarray:
+    """launch_lora_merge on host arrays, all `jobs` in one launch: base_bits [rows][ld_base] (None = in place) and
+    out_bits [rows][ld_out] uint16 words (out_bits = the initial content of the destination); each job a dict
+    (row0, rows, A [r][cols] f32 or None, B [rows_mod][r] f32 or None, eff, map, row_off, half, copy_rest).
+    Returns the destination after the launch.  `lib`: a loaded library that exports the entry (default: the GPU
+    self-test library)."""
+    lib = lib or load_selftest_library()
+    out = np.array(out_bits, dtype=np.uint16, order="C", copy=True)
+    base = None if base_bits is None else np.ascontiguousarray(base_bits, dtype=np.uint16)
+    keep = []
+    arr = (AceMiLoraJob * len(jobs))()
+    for i, j in enumerate(jobs):
+        A = None if j.get("A") is None else np.ascontiguousarray(j["A"], dtype=np.float32)
+        B = None if j.get("B") is None else np.ascontiguousarray(j["B"], dtype=np.float32)
+        keep += [A, B]
+        arr[i] = AceMiLoraJob(row0=int(j["row0"]), rows=int(j["rows"]), r=0 if A is None else int(A.shape[0]),
+                              rows_mod=0 if B is None else int(B.shape[0]), A=_fptr(A), B=_fptr(B),
+                              eff=float(j.get("eff", 0.0)), map=int(j.get("map", 0)), row_off=int(j.get("row_off", 0)),
+                              half=int(j.get("half", 0)), copy_rest=1 if j.get("copy_rest") else 0)
+    u16p = ctypes.POINTER(ctypes.c_uint16)
+    st = lib.ace_mi_kernel_lora_merge({"bf16": 0, "fp16": 1}[fmt], out.shape[0], int(cols),
+                                      0 if base is None else base.shape[1], out.shape[1],
+                                      None if base is None else base.ctypes.data_as(u16p), out.ctypes.data_as(u16p),
+                                      arr, len(jobs))
+    if st != ACE_GGML_OK:
+        raise RuntimeError(f"ace_mi_kernel_lora_merge failed (status={st})")
     return out
 
 

@@ -111,6 +111,86 @@ def install_dit_backend(dit_handler: Any, bridge) -> None:
     decoder.forward = types.MethodType(decoder_forward_mi355x, decoder)
     setattr(dit_handler, "_ggml_dit_backend", "mi355x-capi")
     setattr(dit_handler, "_ggml_dit_decoder_forward_hooked", True)
+    install_lora_backend(dit_handler, bridge)
+
+
+def install_lora_backend(dit_handler: Any, bridge) -> None:
+    """Route the handler's LoRA controls (acestep/core/generation/handler/lora/lifecycle.py:11-106,
+    controls.py:12-115) to the engine.  The reference versions wrap `model.decoder` in a PeftModel, which the hooked
+    decoder.forward never runs, so an adapter loaded through them would be ignored; these drive
+    `bridge.load_lora / set_lora_scale / unload_lora` instead, keep `lora_loaded`, `use_lora` and `lora_scale` as the
+    reference methods do, return status strings in their style, need no `peft` and leave `model.decoder` alone."""
+    import math
+    import os
+
+    for name, default in (("lora_loaded", False), ("use_lora", False), ("lora_scale", 1.0)):
+        if not hasattr(dit_handler, name):
+            setattr(dit_handler, name, default)
+
+    def load_lora_mi355x(self, lora_path: str) -> str:
+        if getattr(self, "model", None) is None:
+            return "❌ Model not initialized. Please initialize service first."
+        if not lora_path or not str(lora_path).strip():
+            return "❌ Please provide a LoRA path."
+        lora_path = str(lora_path).strip()
+        if not os.path.exists(lora_path):
+            return f"❌ LoRA path not found: {lora_path}"
+        if not os.path.exists(os.path.join(lora_path, "adapter_config.json")):
+            return f"❌ Invalid LoRA adapter: adapter_config.json not found in {lora_path}"
+        try:
+            bridge.load_lora(lora_path, float(self.lora_scale))
+        except Exception as e:  # the previous adapter (if any) stays loaded in the engine
+            return f"❌ Failed to load LoRA: {str(e)}"
+        self.lora_loaded = True
+        self.use_lora = True
+        return f"✅ LoRA loaded from {lora_path}"
+
+    def unload_lora_mi355x(self) -> str:
+        if not self.lora_loaded:
+            return "⚠️ No LoRA adapter loaded."
+        try:
+            bridge.unload_lora()
+        except Exception as e:
+            return f"❌ Failed to unload LoRA: {str(e)}"
+        self.lora_loaded = False
+        self.use_lora = False
+        self.lora_scale = 1.0
+        return "✅ LoRA unloaded, using base model"
+
+    def set_use_lora_mi355x(self, use_lora: bool) -> str:
+        if use_lora and not self.lora_loaded:
+            return "❌ No LoRA adapter loaded. Please load a LoRA first."
+        self.use_lora = bool(use_lora)
+        if self.lora_loaded:
+            try:  # off = engine scale 0 (base weights, adapter resident); on = back to the remembered lora_scale
+                bridge.set_lora_scale(float(self.lora_scale) if use_lora else 0.0)
+            except Exception as e:
+                return f"❌ Failed to toggle LoRA: {str(e)}"
+        return f"✅ LoRA {'enabled' if use_lora else 'disabled'}"
+
+    def set_lora_scale_mi355x(self, scale: float) -> str:
+        if not self.lora_loaded:
+            return "⚠️ No LoRA loaded"
+        try:
+            scale_value = float(scale)
+        except (TypeError, ValueError):
+            return "❌ Invalid LoRA scale: please provide a numeric value between 0 and 1."
+        if not math.isfinite(scale_value):
+            return "❌ Invalid LoRA scale: please provide a finite numeric value between 0 and 1."
+        self.lora_scale = max(0.0, min(1.0, scale_value))
+        if not self.use_lora:
+            return f"✅ LoRA scale: {self.lora_scale:.2f} (LoRA disabled)"
+        try:
+            bridge.set_lora_scale(self.lora_scale)
+        except Exception as e:
+            return f"❌ Failed to set LoRA scale: {str(e)}"
+        return f"✅ LoRA scale: {self.lora_scale:.2f}"
+
+    dit_handler.load_lora = types.MethodType(load_lora_mi355x, dit_handler)
+    dit_handler.unload_lora = types.MethodType(unload_lora_mi355x, dit_handler)
+    dit_handler.set_use_lora = types.MethodType(set_use_lora_mi355x, dit_handler)
+    dit_handler.set_lora_scale = types.MethodType(set_lora_scale_mi355x, dit_handler)
+    setattr(dit_handler, "_ggml_lora_backend", "mi355x-capi")
 
 
 def _tile_plan(T: int, chunk_size: int, overlap: int):

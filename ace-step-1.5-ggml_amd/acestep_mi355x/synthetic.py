@@ -409,3 +409,196 @@ def write_gguf(safetensors_path: str, out_path: str, quant: str = "Q8", arch: st
             f.write(b"\0" * ((32 - len(data) % 32) % 32))
     os.replace(tmp, out_path)
     return out_path
+
+
+# ----------------------------------------------------------------------------- PEFT LoRA adapters
+# What peft's save_pretrained writes for the reference trainer (acestep/training/lora_utils.py, configs.py:12-38:
+# r = 8, alpha = 16, targets q_proj,k_proj,v_proj,o_proj): adapter_config.json + adapter_model.safetensors with
+# base_model.model.layers.{i}.{self_attn|cross_attn|mlp}.{x}_proj.lora_{A,B}.weight, A [r][in], B [out][r].
+LORA_ATTN_TARGETS = ("q_proj", "k_proj", "v_proj", "o_proj")
+LORA_MLP_TARGETS = ("gate_proj", "up_proj", "down_proj")
+LORA_ALL_TARGETS = tuple(f"{a}.{p}" for a in ("self_attn", "cross_attn") for p in LORA_ATTN_TARGETS) + \
+    tuple(f"mlp.{p}" for p in LORA_MLP_TARGETS)
+
+
+def lora_module_dims(cfg: dict, module: str) -> Tuple[int, int]:
+    """(in, out) of decoder module "self_attn.q_proj" / "mlp.down_proj" / ..."""
+    H, I, D = cfg["hidden_size"], cfg["intermediate_size"], cfg["head_dim"]
+    qd, kd = cfg["num_attention_heads"] * D, cfg["num_key_value_heads"] * D
+    proj = module.split(".")[-1]
+    return {"q_proj": (H, qd), "k_proj": (H, kd), "v_proj": (H, kd), "o_proj": (qd, H), "gate_proj": (H, I),
+            "up_proj": (H, I), "down_proj": (I, H)}[proj]
+
+
+def _expand_targets(targets) -> Tuple[str, ...]:
+    """Target names as peft takes them: a bare projection ("q_proj") means every block that has one."""
+    out = []
+    for t in targets:
+        if "." in t:
+            out.append(t)
+        elif t in LORA_ATTN_TARGETS:
+            out += [f"self_attn.{t}", f"cross_attn.{t}"]
+        else:
+            out.append(f"mlp.{t}")
+    return tuple(dict.fromkeys(out))
+
+
+def write_lora_adapter(out_dir: str, cfg: dict, r=8, alpha: float = 16.0, targets=LORA_ATTN_TARGETS, seed: int = 0,
+                       dtype: str = "F32", rslora: bool = False, std: float = 0.02, alpha_pattern=None,
+                       key_prefix: str = "base_model.model.", adapter_name: str | None = None,
+                       extra_config=None) -> str:
+    """Write adapter_config.json + adapter_model.safetensors by hand.  A and B ~ N(0, std) (peft initialises B to
+    zero; a non-zero B makes the delta visible).  r: one rank, or a dict module-suffix -> rank (rank_pattern).
+    targets: "q_proj" (self and cross) or "self_attn.q_proj" / "mlp.up_proj".  adapter_name: written as the
+    lora_A.<name>.weight key form."""
+    os.makedirs(out_dir, exist_ok=True)
+    mods = _expand_targets(targets)
+    r_default = r if isinstance(r, int) else 8
+    rank_pattern = {} if isinstance(r, int) else dict(r)
+    conf = dict(peft_type="LORA", task_type=None, base_model_name_or_path=None, r=r_default, lora_alpha=alpha,
+                lora_dropout=0.0, bias="none", target_modules=sorted({m.split(".")[-1] for m in mods}),
+                modules_to_save=None, use_rslora=bool(rslora), use_dora=False, rank_pattern=rank_pattern,
+                alpha_pattern=dict(alpha_pattern or {}), fan_in_fan_out=False, inference_mode=True)
+    conf.update(extra_config or {})
+    with open(os.path.join(out_dir, "adapter_config.json"), "w", encoding="utf-8") as f:
+        json.dump(conf, f, indent=1)
+    rng = np.random.default_rng(seed)
+    tensors = []
+    seg = "" if adapter_name is None else f".{adapter_name}"
+    for i in range(cfg["num_hidden_layers"]):
+        for m in mods:
+            fin, fout = lora_module_dims(cfg, m)
+            name = f"layers.{i}.{m}"
+            rk = r_default
+            for pat, v in rank_pattern.items():
+                if name == pat or name.endswith("." + pat):
+                    rk = int(v)
+            tensors.append((f"{key_prefix}{name}.lora_A{seg}.weight",
+                            rng.standard_normal((rk, fin), dtype=np.float32) * np.float32(std)))
+            tensors.append((f"{key_prefix}{name}.lora_B{seg}.weight",
+                            rng.standard_normal((fout, rk), dtype=np.float32) * np.float32(std)))
+    write_safetensors(os.path.join(out_dir, "adapter_model.safetensors"), tensors, dtype)
+    return out_dir
+
+
+def write_safetensors(path: str, tensors, dtype: str) -> None:
+    """tensors: [(name, f32 array)] written as `dtype` (BF16 / F16 / F32)."""
+    esz = {"BF16": 2, "F16": 2, "F32": 4}[dtype]
+    header: Dict[str, dict] = {}
+    off = 0
+    for name, v in tensors:
+        n = int(v.size) * esz
+        header[name] = {"dtype": dtype, "shape": list(v.shape), "data_offsets": [off, off + n]}
+        off += n
+    hjson = json.dumps(header, separators=(",", ":")).encode("utf-8")
+    hjson += b" " * ((8 - len(hjson) % 8) % 8)
+    tmp = path + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(struct.pack("<Q", len(hjson)))
+        f.write(hjson)
+        for _, v in tensors:
+            f.write(_encode(np.asarray(v, np.float32), dtype))
+    os.replace(tmp, path)
+
+
+def _read_safetensors_raw(path: str):
+    """{name: (dtype, shape, raw words / f32 array)} without widening the 16-bit tensors."""
+    with open(path, "rb") as f:
+        n = struct.unpack("<Q", f.read(8))[0]
+        header = json.loads(f.read(n))
+        base = 8 + n
+        out = {}
+        for name, info in header.items():
+            if name == "__metadata__":
+                continue
+            b0, b1 = info["data_offsets"]
+            f.seek(base + b0)
+            raw = f.read(b1 - b0)
+            dt = info["dtype"]
+            out[name] = (dt, tuple(info["shape"]), np.frombuffer(raw, "<f4" if dt == "F32" else "<u2").copy())
+    return out
+
+
+def lora_acc(A: np.ndarray, B: np.ndarray) -> np.ndarray:
+    """The merge kernel's accumulator [out][in]: acc = 0; for j ascending: acc = acc + B[:, j] * A[j, :], the
+    multiply and the add each rounded to float32 (an explicit loop; `@` would accumulate otherwise)."""
+    A = np.ascontiguousarray(A, np.float32)
+    B = np.ascontiguousarray(B, np.float32)
+    acc = np.zeros((B.shape[0], A.shape[1]), np.float32)
+    for j in range(A.shape[0]):
+        acc = acc + B[:, j:j + 1] * A[j:j + 1, :]
+    return acc
+
+
+def lora_merge_bits(base_bits: np.ndarray, acc: np.ndarray, eff, fmt: str) -> np.ndarray:
+    """rne16(f32(base) + eff * acc) on raw 16-bit words (fmt "BF16" / "F16")."""
+    t = np.float32(eff) * acc.astype(np.float32)
+    if fmt == "F16":
+        w = np.ascontiguousarray(base_bits, "<u2").view("<f2").astype(np.float32)
+        return (w + t).astype("<f2").view("<u2")
+    w = (np.ascontiguousarray(base_bits, "<u2").astype(np.uint32) << 16).view(np.float32)
+    return _bf16_bits(w + t)
+
+
+def lora_eff(scale: float, alpha: float, r: int, rslora: bool = False) -> np.float32:
+    """f32(scale) * f32(alpha / r) (alpha / sqrt(r) with use_rslora), the engine's per-module scale."""
+    unit = np.float32(alpha / np.sqrt(float(r))) if rslora else np.float32(alpha / float(r))
+    return np.float32(scale) * unit
+
+
+def read_lora_adapter(adapter_dir: str) -> Tuple[dict, Dict[str, Tuple[np.ndarray, np.ndarray]]]:
+    """(adapter config, {"layers.0.self_attn.q_proj": (A f32 [r][in], B f32 [out][r])})."""
+    with open(os.path.join(adapter_dir, "adapter_config.json"), "r", encoding="utf-8") as f:
+        conf = json.load(f)
+    raw = _read_safetensors_f32(os.path.join(adapter_dir, "adapter_model.safetensors"))
+    mods: Dict[str, list] = {}
+    for key, v in raw.items():
+        k = key[len("base_model.model."):] if key.startswith("base_model.model.") else key
+        k = k[len("decoder."):] if k.startswith("decoder.") else k
+        parts = k.split(".")
+        which = parts.index("lora_A") if "lora_A" in parts else parts.index("lora_B")
+        name = ".".join(parts[:which])
+        mods.setdefault(name, [None, None])[0 if parts[which] == "lora_A" else 1] = v.astype(np.float32)
+    return conf, {k: (a, b) for k, (a, b) in mods.items()}
+
+
+def merged_checkpoint(base_dir: str, adapter_dir: str, scale: float, out_dir: str) -> str:
+    """A checkpoint whose targeted decoder weights are rne16(f32(W) + eff * acc) in the base's own 16-bit dtype,
+    with the merge kernel's arithmetic restated in numpy (lora_acc / lora_merge_bits); every other tensor is
+    copied bit for bit.  An engine that loads it runs the same kernels on the same weight bits as the engine
+    that loaded base_dir + the adapter at `scale`."""
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(base_dir, "config.json"), "r", encoding="utf-8") as f:
+        cfg_text = f.read()
+    with open(os.path.join(out_dir, "config.json"), "w", encoding="utf-8") as f:
+        f.write(cfg_text)
+    conf, mods = read_lora_adapter(adapter_dir)
+    tensors = _read_safetensors_raw(os.path.join(base_dir, "model.safetensors"))
+    pats = conf.get("alpha_pattern") or {}
+    for name, (A, B) in mods.items():
+        key = f"decoder.{name}.weight"
+        dt, shape, words = tensors[key]
+        if dt not in ("BF16", "F16"):
+            raise ValueError(f"{key}: merged_checkpoint needs a 16-bit base ({dt})")
+        alpha = conf["lora_alpha"]
+        for pat, v in pats.items():
+            if name == pat or name.endswith("." + pat):
+                alpha = v
+        eff = lora_eff(scale, alpha, A.shape[0], bool(conf.get("use_rslora")))
+        merged = lora_merge_bits(words.reshape(shape), lora_acc(A, B), eff, dt)
+        tensors[key] = (dt, shape, merged.reshape(-1))
+    header: Dict[str, dict] = {}
+    off = 0
+    for name, (dt, shape, words) in tensors.items():
+        header[name] = {"dtype": dt, "shape": list(shape), "data_offsets": [off, off + words.nbytes]}
+        off += words.nbytes
+    hjson = json.dumps(header, separators=(",", ":")).encode("utf-8")
+    hjson += b" " * ((8 - len(hjson) % 8) % 8)
+    tmp = os.path.join(out_dir, "model.safetensors.tmp")
+    with open(tmp, "wb") as f:
+        f.write(struct.pack("<Q", len(hjson)))
+        f.write(hjson)
+        for _, (_, _, words) in tensors.items():
+            f.write(words.tobytes())
+    os.replace(tmp, os.path.join(out_dir, "model.safetensors"))
+    return out_dir

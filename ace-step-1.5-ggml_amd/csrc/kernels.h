@@ -105,6 +105,55 @@ struct DequantJob {
 };
 void launch_dequant_bf16_batch(const DequantJob* jobs, int n, hipStream_t s);
 
+// ------------------------------------------------- LoRA merge (kernels/lora.hip)
+// The adapted 16-bit image of a (possibly fused) weight matrix: for module row o and column i
+//   acc = 0; for j = 0 .. r-1 ascending: acc = acc + B[o][j] * A[j][i]   (multiply and add each rounded to f32,
+//   never contracted);  t = eff * acc;  out = rne16(f32(base) + t)  in the matrix's own 16-bit format,
+// so numpy restates it bit for bit (acestep_mi355x/synthetic.py lora_delta_bits).  A job covers the fused rows
+// [row0, row0 + rows) of base / out; the row map places module row o at a fused row inside that range, and the
+// rows of the range that the map does not reach are copied from base when copy_rest is set (left untouched
+// otherwise).  out == base (in place) is allowed; columns >= cols of a row and rows outside the range are never
+// written.  cols, ld_base, ld_out % 8 == 0 and 16-byte aligned base / out / A (16-byte accesses on the matrix).
+enum LoraRowMap : int {
+    LORA_ROWS_PLAIN = 0,       // fused row = row_off + o (row_off: the module's offset inside a q|k|v or k|v concatenation)
+    LORA_ROWS_INTERLEAVE = 1,  // w_gu: fused row = (o / 16) * 32 + half * 16 + o % 16 (half 0 = gate, 1 = up)
+};
+struct LoraMergeJob {
+    int fmt = WF_BF16;  // WF_BF16 | WF_F16, of base and out
+    const uint16_t* base = nullptr;
+    int64_t ld_base = 0;
+    uint16_t* out = nullptr;
+    int64_t ld_out = 0;
+    int row0 = 0, rows = 0, cols = 0;
+    const float* A = nullptr;  // [r][cols]; null (r = 0): no module, the whole range is copy-through
+    const float* B = nullptr;  // [rows_mod][r]
+    int r = 0, rows_mod = 0;
+    float eff = 0.f;
+    int map = LORA_ROWS_PLAIN;
+    int row_off = 0;  // LORA_ROWS_PLAIN
+    int half = 0;     // LORA_ROWS_INTERLEAVE
+    bool copy_rest = false;
+};
+constexpr int LORA_MAX_RANK = 128;
+// module row of fused row fr, or -1 when fr belongs to no row of the job's module
+__host__ __device__ inline int lora_module_row(int map, int row_off, int half, int rows_mod, int r, int fr) {
+    if (r <= 0) return -1;
+    int o;
+    if (map == LORA_ROWS_INTERLEAVE) {
+        if (((fr >> 4) & 1) != half) return -1;
+        o = (fr >> 5) * 16 + (fr & 15);
+    } else {
+        o = fr - row_off;
+    }
+    return (o >= 0 && o < rows_mod) ? o : -1;
+}
+// fused row of module row o (the inverse of lora_module_row)
+__host__ __device__ inline int lora_fused_row(int map, int row_off, int half, int o) {
+    return map == LORA_ROWS_INTERLEAVE ? (o >> 4) * 32 + half * 16 + (o & 15) : row_off + o;
+}
+// any number of jobs (launches of up to 8 jobs each); jobs of one call must not write the same rows
+void launch_lora_merge(const LoraMergeJob* jobs, int n, hipStream_t s);
+
 // ------------------------------------------------- ggml-faithful quantized activations (kernels/gemm_a8.hip)
 // ggml's mul_mat against a quantized weight first converts the f32 activation rows to the weight's vec_dot_type
 // (Q8_0 blocks for Q8_0 weights, Q8_K for K-quants) and takes integer dot products per block

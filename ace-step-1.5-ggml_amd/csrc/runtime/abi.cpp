@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "context.h"
+#include "lora.h"
 
 using namespace acemi_abi;
 
@@ -327,6 +328,64 @@ ace_ggml_status ace_mi_dit_set_attn_precision(ace_ggml_context* ctx, int32_t mod
                                                   acemi::AttnPrecision::F32, acemi::AttnPrecision::F8C,
                                                   acemi::AttnPrecision::PV8};
     ctx->dit->set_attn_precision(modes[mode]);
+    return ACE_GGML_OK;
+}
+
+extern "C++" {
+namespace {
+// load / set-scale / unload share the status mapping of the adapter reader's exceptions (runtime/lora.h)
+template <typename F>
+ace_ggml_status lora_call(ace_ggml_context* ctx, F&& f) {
+    if (!ctx->dit) return set_error(ctx, ACE_GGML_ERR, "dit not loaded");
+    try {
+        bind_device(ctx);
+        f();
+        ACEMI_HIP(hipStreamSynchronize(ctx->stream));
+    } catch (const acemi::IoError& e) {
+        return set_error(ctx, ACE_GGML_ERR_IO, e.what());
+    } catch (const acemi::Unsupported& e) {
+        return set_error(ctx, ACE_GGML_ERR_UNSUPPORTED, e.what());
+    } catch (const acemi::InvalidArg& e) {
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, e.what());
+    } catch (const std::exception& e) {
+        return set_error(ctx, ACE_GGML_ERR, e.what());
+    }
+    return ACE_GGML_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+ace_ggml_status ace_mi_dit_load_lora(ace_ggml_context* ctx, const char* adapter_dir, float scale) {
+    if (!ctx || !adapter_dir) return ACE_GGML_ERR_INVALID_ARG;
+    if (!(scale == scale) || scale - scale != 0.f) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lora scale must be finite");
+    return lora_call(ctx, [&] { ctx->dit->load_lora(adapter_dir, scale, max_layers_env(), ctx->stream); });
+}
+
+ace_ggml_status ace_mi_dit_set_lora_scale(ace_ggml_context* ctx, float scale) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    if (!(scale == scale) || scale - scale != 0.f) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lora scale must be finite");
+    if (ctx->dit && !ctx->dit->lora_loaded()) return set_error(ctx, ACE_GGML_ERR, "lora not loaded");
+    return lora_call(ctx, [&] { ctx->dit->set_lora_scale(scale, ctx->stream); });
+}
+
+ace_ggml_status ace_mi_dit_unload_lora(ace_ggml_context* ctx) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    return lora_call(ctx, [&] { ctx->dit->unload_lora(ctx->stream); });
+}
+
+ace_ggml_status ace_mi_dit_lora_info(ace_ggml_context* ctx, ace_mi_lora_info* out) {
+    if (!ctx || !out) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->dit) return set_error(ctx, ACE_GGML_ERR, "dit not loaded");
+    const auto i = ctx->dit->lora_info();
+    out->loaded = i.loaded ? 1 : 0;
+    out->scale = i.scale;
+    out->lora_alpha = i.lora_alpha;
+    out->min_rank = i.min_rank;
+    out->max_rank = i.max_rank;
+    out->num_modules = i.modules;
+    out->num_images = i.images;
+    out->image_bytes = static_cast<int64_t>(i.image_bytes);
+    out->merge_ms = i.merge_ms;
     return ACE_GGML_OK;
 }
 

@@ -3,13 +3,16 @@
 #include "engine.h"
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <tuple>
 #include <type_traits>
 
+#include "lora.h"
 #include "operands.h"
 
 namespace acemi {
@@ -57,6 +60,7 @@ DitEngine::~DitEngine() {
     for (auto& kv : q8img_)
         if (kv.second.p) (void)hipFree(kv.second.p);
     if (qa16_.p) (void)hipFree(qa16_.p);
+    free_lora();
 }
 
 namespace {
@@ -72,7 +76,8 @@ DitEngine::LayerViews DitEngine::layer_views(int li, bool staged) {
     size_t off = 0;
     for (int i = 0; i < 6; ++i) {
         v[i] = ws[i]->view();
-        if (staged && weight_quantized(ws[i]->fmt)) {
+        if (lora_view(*ws[i], v[i])) {  // the adapted image in place of the resident / staged weights
+        } else if (staged && weight_quantized(ws[i]->fmt)) {
             v[i].fmt = WF_BF16;
             v[i].q = base + off;
             v[i].s = nullptr;
@@ -91,7 +96,8 @@ void DitEngine::stage_layer(int li, hipStream_t st) {
     DequantJob jobs[6];
     int n = 0;
     for (int i = 0; i < 6; ++i) {
-        if (weight_quantized(ws[i]->fmt) && ws[i]->q) {
+        WeightView adapted;
+        if (weight_quantized(ws[i]->fmt) && ws[i]->q && !lora_view(*ws[i], adapted)) {  // (adapted: never read)
             if (n > 0 && ws[i]->fmt != jobs[0].w.fmt) {  // one launch per weight format
                 launch_dequant_bf16_batch(jobs, n, st);
                 n = 0;
@@ -108,6 +114,7 @@ void DitEngine::stage_layer(int li, hipStream_t st) {
 
 WeightView DitEngine::dense_view(const DevWeight& w, hipStream_t s) {
     WeightView v = w.view();
+    if (lora_view(w, v)) return v;
     if (!staged_quant_ || !stage_per_call_ || !weight_quantized(v.fmt) || !v.q) return v;
     Buf& b = img_[v.q];
     if (!b.p) {
@@ -664,5 +671,268 @@ void DitEngine::probe_gemm(int which, int M, int iters, hipStream_t s) {
     }
 }
 
-}  // namespace acemi
+// ---------------------------------------------------------------- LoRA adapters (engine.h)
+bool DitEngine::lora_view(const DevWeight& w, WeightView& v) const {
+    if (!lora_active_ || !w.q) return false;
+    const auto it = lora_img_.find(w.q);
+    if (it == lora_img_.end() || !it->second.p) return false;
+    v.fmt = weight_quantized(w.fmt) ? WF_BF16 : w.fmt;
+    v.q = it->second.p;
+    v.s = nullptr;
+    v.ld = w.cols;
+    return true;
+}
 
+void DitEngine::free_lora() {
+    for (auto& kv : lora_img_)
+        if (kv.second.p) (void)hipFree(kv.second.p);
+    lora_img_.clear();
+    if (lora_ab_) (void)hipFree(lora_ab_);
+    lora_ab_ = nullptr;
+    lora_a_.clear();
+    lora_b_.clear();
+    lora_.reset();
+    lora_scale_ = 0.f;
+    lora_active_ = false;
+    lora_merge_ms_ = 0.0;
+}
+
+DitEngine::LoraInfo DitEngine::lora_info() const {
+    LoraInfo i;
+    if (!lora_) return i;
+    i.loaded = true;
+    i.scale = lora_scale_;
+    i.lora_alpha = lora_->lora_alpha;
+    i.min_rank = lora_->min_rank;
+    i.max_rank = lora_->max_rank;
+    i.modules = (int)lora_->modules.size();
+    for (const auto& kv : lora_img_)
+        if (kv.second.p) {
+            ++i.images;
+            i.image_bytes += kv.second.bytes;
+        }
+    i.merge_ms = lora_merge_ms_;
+    return i;
+}
+
+// The images of the current adapter at the current scale, always from the base weights.  Everything that was
+// computed from the previous views goes: the cached cross K/V and the staged slots (stage_layer leaves the slot of
+// an adapted matrix unwritten, so the next forward expands them again).
+void DitEngine::rebuild_lora_images(hipStream_t s) {
+    ACEMI_HIP(hipDeviceSynchronize());  // a forward in flight (on any stream) reads the current views
+    cross_key_.valid = false;
+    stage_layers_ = 0;
+    lora_active_ = false;
+    lora_merge_ms_ = 0.0;
+    if (!lora_ || lora_scale_ == 0.f) return;
+
+    const DitModel& m = model_;
+    const DitConfig& c = m.cfg;
+    const int H = c.hidden, I = c.intermediate, qd = c.hq * c.head_dim, kd = c.hkv * c.head_dim;
+    std::map<std::tuple<int, int, int>, int> index;
+    for (size_t i = 0; i < lora_->modules.size(); ++i) {
+        const LoraModule& lm = lora_->modules[i];
+        index[std::make_tuple(lm.layer, lm.block, lm.proj)] = (int)i;
+    }
+    struct Slot {  // one module's rows inside a fused matrix
+        int map, row_off, half, rows_mod, mod;
+    };
+    std::vector<std::pair<const DevWeight*, std::vector<Slot>>> mats;
+    auto slot = [&](std::vector<Slot>& v, int li, int block, int proj, int map, int row_off, int half, int rows_mod) {
+        const auto it = index.find(std::make_tuple(li, block, proj));
+        v.push_back(Slot{map, row_off, half, rows_mod, it == index.end() ? -1 : it->second});
+    };
+    const bool ckv_fused = m.w_ckv_all.q != nullptr;
+    std::vector<Slot> ckv_all;
+    for (int li = 0; li < (int)m.layers.size(); ++li) {
+        const DevLayer& ly = m.layers[li];
+        std::vector<Slot> v;
+        slot(v, li, LORA_SELF, LORA_Q, LORA_ROWS_PLAIN, 0, 0, qd);
+        slot(v, li, LORA_SELF, LORA_K, LORA_ROWS_PLAIN, qd, 0, kd);
+        slot(v, li, LORA_SELF, LORA_V, LORA_ROWS_PLAIN, qd + kd, 0, kd);
+        mats.emplace_back(&ly.w_qkv, v);
+        v.clear();
+        slot(v, li, LORA_SELF, LORA_O, LORA_ROWS_PLAIN, 0, 0, H);
+        mats.emplace_back(&ly.w_o, v);
+        v.clear();
+        slot(v, li, LORA_CROSS, LORA_Q, LORA_ROWS_PLAIN, 0, 0, qd);
+        mats.emplace_back(&ly.w_cq, v);
+        v.clear();
+        std::vector<Slot>& kv = ckv_fused ? ckv_all : v;
+        const int r0 = ckv_fused ? li * 2 * kd : 0;  // layer li's k|v rows inside w_ckv_all
+        slot(kv, li, LORA_CROSS, LORA_K, LORA_ROWS_PLAIN, r0, 0, kd);
+        slot(kv, li, LORA_CROSS, LORA_V, LORA_ROWS_PLAIN, r0 + kd, 0, kd);
+        if (!ckv_fused) mats.emplace_back(&ly.w_ckv, v);
+        v.clear();
+        slot(v, li, LORA_CROSS, LORA_O, LORA_ROWS_PLAIN, 0, 0, H);
+        mats.emplace_back(&ly.w_co, v);
+        v.clear();
+        slot(v, li, LORA_MLP, LORA_GATE, LORA_ROWS_INTERLEAVE, 0, 0, I);
+        slot(v, li, LORA_MLP, LORA_UP, LORA_ROWS_INTERLEAVE, 0, 1, I);
+        mats.emplace_back(&ly.w_gu, v);
+        v.clear();
+        slot(v, li, LORA_MLP, LORA_DOWN, LORA_ROWS_PLAIN, 0, 0, H);
+        mats.emplace_back(&ly.w_down, v);
+    }
+    if (ckv_fused) mats.emplace_back(&m.w_ckv_all, ckv_all);
+
+    // allocate first (ensure() synchronises the device), then launch everything in stream order
+    std::vector<LoraMergeJob> jobs;
+    std::vector<const DevWeight*> expand;
+    for (const auto& mt : mats) {
+        const DevWeight& w = *mt.first;
+        bool any = false;
+        for (const Slot& sl : mt.second) any = any || sl.mod >= 0;
+        if (!any) continue;
+        ACEMI_CHECK(w.q && w.fmt != WF_F32X3, "lora: the targeted weight is not a 16-bit or block-format matrix");
+        Buf& img = lora_img_[w.q];
+        ensure(img, (size_t)w.rows * w.cols * 2);
+        const bool quantized = weight_quantized(w.fmt);
+        if (quantized) expand.push_back(&w);
+        for (size_t k = 0; k < mt.second.size(); ++k) {
+            const Slot& sl = mt.second[k];
+            LoraMergeJob j;
+            j.fmt = quantized ? WF_BF16 : w.fmt;
+            j.base = quantized ? static_cast<const uint16_t*>(img.p) : static_cast<const uint16_t*>(w.q);
+            j.out = static_cast<uint16_t*>(img.p);
+            j.ld_base = j.ld_out = w.cols;
+            j.cols = w.cols;
+            j.map = sl.map;
+            j.row_off = sl.row_off;
+            j.half = sl.half;
+            if (sl.map == LORA_ROWS_INTERLEAVE) {  // the job's range is the whole matrix; the other half is copied by
+                j.row0 = 0;                        // its own job, or by this one when it has no adapter
+                j.rows = w.rows;
+                const Slot& other = mt.second[k ^ 1];
+                j.copy_rest = other.mod < 0;
+                if (sl.mod < 0) continue;
+            } else {
+                j.row0 = sl.row_off;
+                j.rows = sl.rows_mod;
+                j.copy_rest = sl.mod < 0;  // a module without an adapter: its rows are copied through
+            }
+            if (sl.mod >= 0) {
+                const LoraModule& lm = lora_->modules[sl.mod];
+                ACEMI_CHECK(lm.in == w.cols && lm.out == sl.rows_mod, "lora: module shape does not match the weight");
+                j.A = lora_a_[sl.mod];
+                j.B = lora_b_[sl.mod];
+                j.r = lm.r;
+                j.rows_mod = sl.rows_mod;
+                j.eff = lora_scale_ * lm.unit;
+            } else if (quantized) {
+                continue;  // in place: the rows are in the image already
+            }
+            jobs.push_back(j);
+        }
+    }
+    ACEMI_HIP(hipDeviceSynchronize());
+    const auto t0 = std::chrono::steady_clock::now();
+    for (const DevWeight* w : expand)
+        launch_dequant_bf16(w->view(), w->rows, w->cols, static_cast<uint16_t*>(lora_img_[w->q].p), s);
+    launch_lora_merge(jobs.data(), (int)jobs.size(), s);
+    ACEMI_HIP(hipStreamSynchronize(s));
+    lora_merge_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    lora_active_ = true;
+}
+
+void DitEngine::load_lora(const std::string& dir, float scale, int max_layers, hipStream_t s) {
+    if (qact_)
+        throw Unsupported("lora: the quantized-activation parity mode (ACE_MI_QUANT_ACT=q8) multiplies the block "
+                          "weights themselves and cannot run an adapter");
+    auto ad = std::make_unique<LoraAdapter>(read_lora_adapter(dir, model_.cfg, max_layers));  // throws: state unchanged
+    ACEMI_HIP(hipDeviceSynchronize());
+    free_lora();
+    // A and B of every module in one device buffer (256-byte aligned parts)
+    size_t total = 0;
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    for (const LoraModule& lm : ad->modules) total += al(lm.A.size() * 4) + al(lm.B.size() * 4);
+    std::vector<char> host(total);
+    ACEMI_HIP(hipMalloc(&lora_ab_, total));
+    size_t off = 0;
+    for (LoraModule& lm : ad->modules) {
+        std::memcpy(&host[off], lm.A.data(), lm.A.size() * 4);
+        lora_a_.push_back(reinterpret_cast<const float*>(static_cast<char*>(lora_ab_) + off));
+        off += al(lm.A.size() * 4);
+        std::memcpy(&host[off], lm.B.data(), lm.B.size() * 4);
+        lora_b_.push_back(reinterpret_cast<const float*>(static_cast<char*>(lora_ab_) + off));
+        off += al(lm.B.size() * 4);
+        lm.A = std::vector<float>();
+        lm.B = std::vector<float>();
+    }
+    ACEMI_HIP(hipMemcpy(lora_ab_, host.data(), total, hipMemcpyHostToDevice));
+    ACEMI_HIP(hipDeviceSynchronize());  // null-stream copy: done before any stream reads it
+    lora_ = std::move(ad);
+    lora_scale_ = scale;
+    try {
+        rebuild_lora_images(s);
+    } catch (...) {
+        free_lora();
+        throw;
+    }
+}
+
+void DitEngine::set_lora_scale(float scale, hipStream_t s) {
+    ACEMI_CHECK(lora_ != nullptr, "lora not loaded");
+    lora_scale_ = scale;
+    rebuild_lora_images(s);
+}
+
+void DitEngine::unload_lora(hipStream_t s) {
+    ACEMI_HIP(hipDeviceSynchronize());
+    free_lora();
+    rebuild_lora_images(s);  // (nothing loaded: drops what was computed from the adapted views)
+}
+
+#ifndef __HIP__
+// Host build of the runtime (no device compiler: the CPU tests' library, whose other launch_* are host loops too):
+// launch_lora_merge as plain loops with the arithmetic of kernels.h, on "device" memory that is host memory.  The
+// translation unit is compiled without FMA contraction, so each multiply and add below rounds on its own.
+void launch_lora_merge(const LoraMergeJob* jobs, int n, hipStream_t) {
+    auto widen = [](int fmt, uint16_t b) {
+        if (fmt == WF_F16) return half_to_f32(b);
+        const uint32_t u = (uint32_t)b << 16;
+        float f;
+        std::memcpy(&f, &u, 4);
+        return f;
+    };
+    auto narrow = [](int fmt, float f) -> uint16_t {
+        if (fmt == WF_F16) {
+            const _Float16 h = (_Float16)f;
+            uint16_t u;
+            std::memcpy(&u, &h, 2);
+            return u;
+        }
+        uint32_t u;
+        std::memcpy(&u, &f, 4);
+        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 64u);
+        u += 0x7fffu + ((u >> 16) & 1u);
+        return (uint16_t)(u >> 16);
+    };
+    for (int ji = 0; ji < n; ++ji) {
+        const LoraMergeJob& j = jobs[ji];
+        ACEMI_CHECK((j.fmt == WF_BF16 || j.fmt == WF_F16) && j.base && j.out && j.rows > 0 && j.cols > 0 &&
+                        j.r >= 0 && j.r <= LORA_MAX_RANK && (j.r == 0 || (j.A && j.B)),
+                    "lora_merge: bad job");
+        for (int fr = j.row0; fr < j.row0 + j.rows; ++fr) {
+            const int o = lora_module_row(j.map, j.row_off, j.half, j.rows_mod, j.r, fr);
+            const uint16_t* src = j.base + (int64_t)fr * j.ld_base;
+            uint16_t* dst = j.out + (int64_t)fr * j.ld_out;
+            if (o < 0) {
+                if (j.copy_rest && src != dst) std::memmove(dst, src, (size_t)j.cols * 2);
+                continue;
+            }
+            for (int i = 0; i < j.cols; ++i) {
+                volatile float acc = 0.f;  // (volatile: one rounded f32 per step, whatever the optimiser prefers)
+                for (int k = 0; k < j.r; ++k) {
+                    const float p = j.B[(int64_t)o * j.r + k] * j.A[(int64_t)k * j.cols + i];
+                    acc = acc + p;
+                }
+                const float t = j.eff * acc;
+                dst[i] = narrow(j.fmt, widen(j.fmt, src[i]) + t);
+            }
+        }
+    }
+}
+#endif
+
+}  // namespace acemi

@@ -9,6 +9,7 @@
 
 #include <map>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "../kernels.h"
@@ -16,6 +17,8 @@
 #include "model.h"
 
 namespace acemi {
+
+struct LoraAdapter;  // runtime/lora.h
 
 struct ForwardIO {
     int B = 1, T = 0, L = 0;
@@ -97,6 +100,24 @@ class DitEngine {
     void reset_times();
     // launch only the MLP gate/up GEMM of layer 0 for a given M (bench / roofline probe)
     void probe_gemm(int which, int M, int iters, hipStream_t s);
+    // PEFT LoRA adapter (runtime/lora.h reads it): every fused block matrix / the cross k|v matrix that holds a
+    // targeted module gets an adapted 16-bit image rne16(W + eff * B.A) (launch_lora_merge; a quantized matrix is
+    // expanded to its bf16 image first and merged in place), and layer_views / dense_view hand that image to the
+    // GEMMs in place of the resident or staged weights: same kernels, same launches, nothing per step.  The base
+    // weights are never written, so a scale change rebuilds from them and unload is exact.  All three block until
+    // the device is idle (a forward in flight reads the current views).  max_layers: ACE_GGML_DIT_MAX_LAYERS.
+    struct LoraInfo {
+        bool loaded = false;
+        float scale = 0.f, lora_alpha = 0.f;
+        int min_rank = 0, max_rank = 0, modules = 0, images = 0;
+        size_t image_bytes = 0;
+        double merge_ms = 0.0;
+    };
+    void load_lora(const std::string& dir, float scale, int max_layers, hipStream_t s);
+    void set_lora_scale(float scale, hipStream_t s);
+    void unload_lora(hipStream_t s);
+    bool lora_loaded() const { return lora_ != nullptr; }
+    LoraInfo lora_info() const;
 
    private:
     struct Buf {
@@ -195,6 +216,18 @@ class DitEngine {
     char* stage_slot(int li);
     LayerViews layer_views(int li, bool staged);
     void stage_layer(int li, hipStream_t st);
+    // LoRA state: the adapter's A / B in one device buffer (lora_ab_), the adapted images keyed like img_ by the
+    // resident weight pointer; lora_active_ = an adapter is loaded at a non-zero scale (the views use the images)
+    std::unique_ptr<LoraAdapter> lora_;
+    std::vector<const float*> lora_a_, lora_b_;  // device A / B of lora_->modules[i]
+    void* lora_ab_ = nullptr;
+    float lora_scale_ = 0.f;
+    bool lora_active_ = false;
+    double lora_merge_ms_ = 0.0;
+    std::map<const void*, Buf> lora_img_;
+    bool lora_view(const DevWeight& w, WeightView& v) const;
+    void rebuild_lora_images(hipStream_t s);
+    void free_lora();
     struct Fault {  // ACE_MI_TEST_FAULT (test-only fault injection); layer -1 = off
         int layer = -1, row = 0, col = 0;
         float amp = 0.f;

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstring>
 #include <cstdlib>
+#include <memory>
 #include <vector>
 
 #include "../../../include/acestep_mi355x_selftest.h"
@@ -331,6 +332,65 @@ ace_ggml_status ace_mi_kernel_dequant(int32_t qtype, int32_t N, int32_t K, const
         ACEMI_HIP(hipMemcpy(out, dout.p, (size_t)N * K * 2, hipMemcpyDeviceToHost));
     } catch (const std::exception& ex) {
         std::fprintf(stderr, "ace_mi_kernel_dequant: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+// LoRA merge kernel: n_jobs jobs of one launch on one host matrix pair (include/acestep_mi355x_selftest.h).
+ace_ggml_status ace_mi_kernel_lora_merge(int32_t fmt, int32_t total_rows, int32_t cols, int32_t ld_base, int32_t ld_out,
+                                         const uint16_t* base, uint16_t* out, const ace_mi_lora_job* jobs,
+                                         int32_t n_jobs) {
+    using namespace acemi;
+    if (!out || !jobs || n_jobs <= 0 || total_rows <= 0 || cols <= 0 || ld_out < cols || (base && ld_base < cols) ||
+        (fmt != 0 && fmt != 1))
+        return ACE_GGML_ERR_INVALID_ARG;
+    for (int i = 0; i < n_jobs; ++i) {  // every row a job may touch lies inside the host matrices
+        const ace_mi_lora_job& j = jobs[i];
+        if (j.row0 < 0 || j.rows <= 0 || j.row0 + j.rows > total_rows || j.r < 0 || (j.r > 0 && (!j.A || !j.B || j.rows_mod <= 0)))
+            return ACE_GGML_ERR_INVALID_ARG;
+    }
+    try {
+        const size_t nb = (size_t)total_rows * (base ? ld_base : ld_out) * 2, no = (size_t)total_rows * ld_out * 2;
+        DevMem dbase(base ? nb : 16), dout(no);
+        if (base) ACEMI_HIP(hipMemcpy(dbase.p, base, nb, hipMemcpyHostToDevice));
+        ACEMI_HIP(hipMemcpy(dout.p, out, no, hipMemcpyHostToDevice));
+        std::vector<std::unique_ptr<DevMem>> ab;
+        std::vector<LoraMergeJob> lj(n_jobs);
+        for (int i = 0; i < n_jobs; ++i) {
+            const ace_mi_lora_job& j = jobs[i];
+            LoraMergeJob& d = lj[i];
+            d.fmt = fmt == 1 ? WF_F16 : WF_BF16;
+            d.base = base ? dbase.as<uint16_t>() : dout.as<uint16_t>();
+            d.ld_base = base ? ld_base : ld_out;
+            d.out = dout.as<uint16_t>();
+            d.ld_out = ld_out;
+            d.row0 = j.row0;
+            d.rows = j.rows;
+            d.cols = cols;
+            d.r = j.r;
+            d.rows_mod = j.rows_mod;
+            d.eff = j.eff;
+            d.map = j.map;
+            d.row_off = j.row_off;
+            d.half = j.half;
+            d.copy_rest = j.copy_rest != 0;
+            if (j.r > 0) {
+                const size_t na = (size_t)j.r * cols * 4, nbb = (size_t)j.rows_mod * j.r * 4;
+                ab.emplace_back(new DevMem(na));
+                ACEMI_HIP(hipMemcpy(ab.back()->p, j.A, na, hipMemcpyHostToDevice));
+                d.A = ab.back()->as<float>();
+                ab.emplace_back(new DevMem(nbb));
+                ACEMI_HIP(hipMemcpy(ab.back()->p, j.B, nbb, hipMemcpyHostToDevice));
+                d.B = ab.back()->as<float>();
+            }
+        }
+        ACEMI_HIP(hipDeviceSynchronize());
+        launch_lora_merge(lj.data(), n_jobs, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        ACEMI_HIP(hipMemcpy(out, dout.p, no, hipMemcpyDeviceToHost));
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lora_merge: %s\n", ex.what());
         return ACE_GGML_ERR;
     }
     return ACE_GGML_OK;

@@ -84,6 +84,40 @@ ACE_GGML_API ace_ggml_status ace_mi_dit_sample_ex(ace_ggml_context* ctx, int32_t
  * 4 = `pv8` (fp16 Q.K, P.V as in f8c).  All accumulate in f32. */
 ACE_GGML_API ace_ggml_status ace_mi_dit_set_attn_precision(ace_ggml_context* ctx, int32_t mode);
 
+/* ---- PEFT LoRA adapters on the DiT decoder (the reference handler's load_lora / set_lora_scale / unload_lora,
+ * acestep/core/generation/handler/lora/lifecycle.py:30-98).  `adapter_dir` holds adapter_config.json and
+ * adapter_model.safetensors as peft writes them: lora_A [r][in] / lora_B [out][r] (F32, BF16 or F16) for the q/k/v/o
+ * projections of self_attn / cross_attn and the gate/up/down projections of mlp of decoder layers, r <= 128, per-module
+ * ranks, lora_alpha / alpha_pattern / use_rslora honoured.  The engine builds an adapted 16-bit image
+ * rne16(W + scale * alpha / r * B.A) of every weight matrix that holds a targeted module and runs its unchanged kernels
+ * on the images, so an adapter costs nothing per step; the base weights are never modified.  Anything the engine cannot
+ * apply is refused (nothing is skipped silently): ACE_GGML_ERR_IO for a missing file, ACE_GGML_ERR_UNSUPPORTED for
+ * DoRA, bias != "none", modules_to_save, a non-LoRA peft_type, a tensor of a module the engine does not hold or the
+ * quantized-activation mode (ACE_MI_QUANT_ACT=q8), ACE_GGML_ERR_INVALID_ARG for an unpaired, mis-shaped, rank > 128
+ * or non-finite tensor; ace_ggml_last_error names the file or tensor.  A failed load leaves the previous state.
+ * All three calls below are synchronous (the device is idle and the context stream drained on return), return
+ * ACE_GGML_ERR "dit not loaded" without a model, and must not run concurrently with a forward of the context.
+ * ace_ggml_load_dit and ace_ggml_destroy drop the adapter. */
+typedef struct ace_mi_lora_info {
+    int32_t loaded;          /* 1 while an adapter is resident (also at scale 0) */
+    float scale;             /* current strength (0 = the base weights are used) */
+    float lora_alpha;        /* adapter_config.json lora_alpha */
+    int32_t min_rank;
+    int32_t max_rank;
+    int32_t num_modules;     /* adapted projections */
+    int32_t num_images;      /* adapted weight matrices held as 16-bit images */
+    int64_t image_bytes;     /* device memory of the images */
+    double merge_ms;         /* host wall time of the last image build (launch to completion) */
+} ace_mi_lora_info;
+/* Load (replacing any previous adapter) at strength `scale`. */
+ACE_GGML_API ace_ggml_status ace_mi_dit_load_lora(ace_ggml_context* ctx, const char* adapter_dir, float scale);
+/* Rebuild the images from the base weights at a new strength; 0 routes every matrix back to its base weights and
+ * keeps the adapter resident.  ACE_GGML_ERR "lora not loaded" without an adapter. */
+ACE_GGML_API ace_ggml_status ace_mi_dit_set_lora_scale(ace_ggml_context* ctx, float scale);
+/* Drop the adapter and its images (OK when nothing is loaded). */
+ACE_GGML_API ace_ggml_status ace_mi_dit_unload_lora(ace_ggml_context* ctx);
+ACE_GGML_API ace_ggml_status ace_mi_dit_lora_info(ace_ggml_context* ctx, ace_mi_lora_info* out);
+
 /* Per-kernel-class timing with hipEvents on the launch stream (adds a sync per kernel).
  * ace_mi_profile_get copies up to `cap` entries: names (NUL-separated into `names`, `names_cap`
  * bytes), total milliseconds and launch counts.  Returns the number of classes in *n_out. */

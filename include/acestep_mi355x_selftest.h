@@ -65,6 +65,25 @@ ACE_GGML_API ace_ggml_status ace_mi_kernel_gemm_a8_mode(int32_t mode);
  * (the two-waves-per-SIMD kernel for blocks of >= 16 key tiles), 0 = the one-wave-per-SIMD kernel, 1 = the two-wave
  * kernel everywhere.  Same results within the f8c bound. */
 ACE_GGML_API ace_ggml_status ace_mi_kernel_attn_kh(int32_t mode);
+/* LoRA merge kernel (launch_lora_merge, csrc/kernels.h): n_jobs jobs in ONE launch on one matrix pair.  base
+ * [total_rows][ld_base] (NULL = in place on out) and out [total_rows][ld_out] are raw 16-bit words of fmt (0 bf16,
+ * 1 fp16); out holds its initial content on entry and the merged image on return, so a caller sees which words were
+ * written.  A job covers the fused rows [row0, row0 + rows): module row o (A [r][cols], B [rows_mod][r] f32 host
+ * arrays) lands at fused row row_off + o (map 0) or (o / 16) * 32 + half * 16 + o % 16 (map 1, the gate|up
+ * interleave); rows of the range that belong to no module row are copied from base when copy_rest != 0; r = 0 (A, B
+ * NULL) is a copy-only job.  out = rne16(f32(base) + eff * acc), acc the rank-ordered chain of separately rounded f32
+ * multiplies and adds. */
+typedef struct ace_mi_lora_job {
+    int32_t row0, rows;
+    int32_t r, rows_mod;
+    const float* A;
+    const float* B;
+    float eff;
+    int32_t map, row_off, half, copy_rest;
+} ace_mi_lora_job;
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lora_merge(int32_t fmt, int32_t total_rows, int32_t cols, int32_t ld_base,
+                                                      int32_t ld_out, const uint16_t* base, uint16_t* out,
+                                                      const ace_mi_lora_job* jobs, int32_t n_jobs);
 /* Dequant-fused GEMM micro-benchmark: average ms per launch (HIP events). */
 ACE_GGML_API ace_ggml_status ace_mi_bench_gemm_q(int32_t qtype, int32_t epi, int32_t variant, int32_t M, int32_t N,
                                                  int32_t K, int32_t iters, float* avg_ms);
