@@ -48,7 +48,8 @@ EXPORTED_SYMBOLS = (
 # product objects + the kernel self-test / micro-benchmark entries); the product library does not export them.
 SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_bench_attention", "ace_mi_bench_gemm",
                     "ace_mi_kernel_gemm_q", "ace_mi_kernel_dequant", "ace_mi_bench_gemm_q", "ace_mi_kernel_gemm_a8",
-                    "ace_mi_kernel_gemm_a8_mode", "ace_mi_kernel_attn_kh", "ace_mi_kernel_lora_merge")
+                    "ace_mi_kernel_gemm_a8_mode", "ace_mi_kernel_attn_kh", "ace_mi_kernel_lora_merge",
+                    "ace_mi_gemm_resolve", "ace_mi_gemm_variant_row", "ace_mi_gemm_variant_arg_ok")
 
 # qtype codes of ace_mi_quantize & co. (names as parse_quant_type, acestep_dit_model.cpp:27-37)
 QTYPES = {"q8_0": 1, "q4_k": 2, "q6_k": 3}
@@ -212,6 +213,17 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
 _SELFTEST = None
 
 
+def _bind_gemm_variants(lib: ctypes.CDLL) -> ctypes.CDLL:
+    i32, ip = ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)
+    lib.ace_mi_gemm_resolve.argtypes = [i32, i32, i32, i32, i32, i32, i32, ip]
+    lib.ace_mi_gemm_resolve.restype = ctypes.c_int
+    lib.ace_mi_gemm_variant_row.argtypes = [i32, ip, ctypes.c_char_p, ctypes.c_size_t]
+    lib.ace_mi_gemm_variant_row.restype = ctypes.c_int
+    lib.ace_mi_gemm_variant_arg_ok.argtypes = [i32, i32]
+    lib.ace_mi_gemm_variant_arg_ok.restype = ctypes.c_int
+    return lib
+
+
 def selftest_library_path() -> str:
     """Path of the TEST library (a superset of the product ABI that also reads the test-only environment hooks,
     runtime/test_hooks.cpp)."""
@@ -257,6 +269,7 @@ def load_selftest_library() -> ctypes.CDLL:
     lib.ace_mi_kernel_attn_kh.restype = ctypes.c_int
     lib.ace_mi_kernel_lora_merge.argtypes = [i32, i32, i32, i32, i32, u16p, u16p, ctypes.POINTER(AceMiLoraJob), i32]
     lib.ace_mi_kernel_lora_merge.restype = ctypes.c_int
+    _bind_gemm_variants(lib)
     _SELFTEST = lib
     return lib
 
@@ -831,6 +844,41 @@ def gemm_variant(variant: int) -> None:
     lib = load_library()
     if lib.ace_mi_gemm_variant(int(variant)) != ACE_GGML_OK:
         raise ValueError(variant)
+
+
+WFMT = {"bf16": 0, "f16": 1, "q8_0": 2, "q4_k": 3, "q6_k": 4}  # WeightFormat of csrc/kernels.h
+GEMM_FAMILIES = ("none", "gemm_kernel", "gemm8_kernel", "gemm_ws_kernel", "gemm_q_kernel", "gemm_qr_kernel",
+                 "gemm_wsq_kernel")
+
+
+def gemm_resolve(M: int, N: int, K: int, wfmt: str = "bf16", prep: bool = False, forced: int = -1, override: int = -1,
+                 lib=None) -> int:
+    """The variant launch_gemm would launch (csrc/gemm_variants.h): pure, no device.  `lib`: a loaded library that
+    exports the entry, bound or not (default: the GPU self-test library)."""
+    lib = _bind_gemm_variants(lib) if lib is not None else load_selftest_library()
+    v = ctypes.c_int32(-1)
+    st = lib.ace_mi_gemm_resolve(int(forced), int(override), int(M), int(N), int(K), WFMT[wfmt], int(bool(prep)), ctypes.byref(v))
+    if st != ACE_GGML_OK:
+        raise ValueError((M, N, K, wfmt))
+    return v.value
+
+
+def gemm_variant_row(vid: int, lib=None) -> Optional[dict]:
+    """The row of base id `vid` in the variant table, or None: {"name", "dense", "quant" (family name, BM, BN, WM, WN,
+    depth), "dense_split", "quant_split", "prep_sibling", "needs_n256"}."""
+    lib = _bind_gemm_variants(lib) if lib is not None else load_selftest_library()
+    f = (ctypes.c_int32 * 16)()
+    name = ctypes.create_string_buffer(160)
+    if lib.ace_mi_gemm_variant_row(int(vid), f, name, len(name)) != ACE_GGML_OK:
+        return None
+    kern = lambda k: (GEMM_FAMILIES[k[0]],) + tuple(k[1:])
+    return {"name": name.value.decode(), "dense": kern(f[0:6]), "quant": kern(f[6:12]), "dense_split": f[12],
+            "quant_split": f[13], "prep_sibling": f[14], "needs_n256": bool(f[15])}
+
+
+def gemm_variant_arg_ok(variant: int, allow_unchecked: bool = False, lib=None) -> bool:
+    lib = _bind_gemm_variants(lib) if lib is not None else load_selftest_library()
+    return lib.ace_mi_gemm_variant_arg_ok(int(variant), int(allow_unchecked)) == ACE_GGML_OK
 
 
 def kernel_attn_kh(mode: int) -> None:

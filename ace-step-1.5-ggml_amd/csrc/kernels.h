@@ -87,8 +87,8 @@ void launch_gemm(const uint16_t* A, int lda, const WeightView& W, int M, int N, 
 // dense shorthand: W 16-bit of type t
 void launch_gemm(ActType t, const uint16_t* A, int lda, const uint16_t* W, int ldw, int M, int N, int K,
                  const GemmEpilogue& epi, hipStream_t s);
-// -1 = automatic tile choice; 0..11 force a kernel variant, + 100 * S (S = 2..4) split-K over S blocks per
-// tile for the 4-wave tiles (micro-benchmarks / tests)
+// -1 = automatic tile choice; else force a variant of gemm_variants.h (dense ids 0..16 and 18, quantized 0..5, 7 and
+// 20..25, + 100 * S for split-K over S = 2..4 blocks per tile) wherever it handles the shape (micro-benchmarks / tests)
 void gemm_force_variant(int v);
 // Throws (once) if a split-K GEMM join on the current device timed out since the last check: reads a per-device
 // host-pinned error word, no stream is synchronised (called at the library's synchronisation points and on entry).

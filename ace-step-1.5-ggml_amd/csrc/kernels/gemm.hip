@@ -714,33 +714,31 @@ void splitk_setup(GemmParams& p, int ntiles, int S, size_t tile_bytes, hipStream
     p.sk_err = err_dev;
 }
 
-template <int BM, int BN, int WM, int WN, bool F16, int EPI, int PIPE>
+// SK: the tile has split-K instances (a row whose dense_split > 1)
+template <int BM, int BN, int WM, int WN, bool F16, int EPI, int PIPE, bool SK>
 void launch_cfg(GemmParams p, int S, hipStream_t s) {
+    static_assert(!SK || (WM * WN == 4 && PIPE >= 1), "split-K is for the 4-wave pipelined tiles");
     const int nbm = (p.M + BM - 1) / BM;
     const int nbn = p.N / BN;
-    if (S > 1) {
-        if (p.K / 64 < 2 * S) throw std::runtime_error("gemm: split-K needs at least two K-tiles per part");
-        if (S > SplitKMax<BM, BN>::value) throw std::runtime_error("gemm: split-K factor too large for this tile");
-        splitk_setup(p, nbm * nbn, S, (size_t)BM * BN * 4, s);
-    }
     const dim3 grid(nbm * nbn * (S > 1 ? S : 1));
     const dim3 block(WM * WN * 64);
     if constexpr (EPI == EPI_QKV_PREP && BN != 128) {
         throw std::runtime_error("gemm: the fused attention prep needs 128-wide column tiles");
-    } else if constexpr (WM * WN == 4 && PIPE >= 1) {  // split-K instances: the 4-wave pipelined tiles
-        if (S > 1)
-            hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, F16, EPI, PIPE, true>), grid, block, 0, s, p);
-        else
-            hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, F16, EPI, PIPE>), grid, block, 0, s, p);
     } else {
-        if (S > 1) throw std::runtime_error("gemm: split-K is for the 4-wave pipelined tiles");
+        if constexpr (SK) {
+            if (S > 1) {
+                if (S > SplitKMax<BM, BN>::value) throw std::runtime_error("gemm: split-K factor too large for this tile");
+                splitk_setup(p, nbm * nbn, S, (size_t)BM * BN * 4, s);
+                hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, F16, EPI, PIPE, true>), grid, block, 0, s, p);
+                return;
+            }
+        }
         hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, F16, EPI, PIPE>), grid, block, 0, s, p);
     }
 }
 
 template <int BM, int BN, bool F16, int EPI, int NS>
 void launch_ws(const GemmParams& p, hipStream_t s) {
-    if (p.N % BN != 0) throw std::runtime_error("gemm: the warp-specialized tile needs N % BN == 0");
     if constexpr (EPI == EPI_QKV_PREP && BN != 128) {
         throw std::runtime_error("gemm: the fused attention prep needs 128-wide column tiles");
     } else {
@@ -751,11 +749,8 @@ void launch_ws(const GemmParams& p, hipStream_t s) {
 
 template <int BM, bool F16, int EPI>
 void launch_cfg8(GemmParams p, int S, hipStream_t s) {
-    if (p.N % 256 != 0) throw std::runtime_error("gemm: the 8-wave tiles need N % 256 == 0");
     const int nbm = (p.M + BM - 1) / BM;
-    if (S > 1) {
-        if (S != 2) throw std::runtime_error("gemm: the ping-pong tiles split K over two parts only");
-        if (p.K / 64 < 2 * S) throw std::runtime_error("gemm: split-K needs at least two K-tiles per part");
+    if (S > 1) {  // (over two parts: SplitKMax<BM, 256>)
         splitk_setup(p, nbm * (p.N / 256), S, (size_t)BM * 256 * 4, s);
         hipLaunchKernelGGL((gemm8_kernel<BM, F16, EPI, true>), dim3(nbm * (p.N / 256) * S), dim3(512), 0, s, p);
         return;
@@ -763,56 +758,24 @@ void launch_cfg8(GemmParams p, int S, hipStream_t s) {
     hipLaunchKernelGGL((gemm8_kernel<BM, F16, EPI>), dim3(nbm * (p.N / 256)), dim3(512), 0, s, p);
 }
 
-// variant: 0 = 128x128 PIPE0, 1 = 128x128 PIPE1, 2 = 256x256 PIPE1 (8 waves 2x4), 3 = 256x128 PIPE1,
-// 4 = 192x128 PIPE1, 5 = 192x256 PIPE1 (8 waves 2x4), 6 = 192x64 PIPE1 (dense only), 7 = 96x128 PIPE1,
-// 8 = 64x128 PIPE1, 9 = 64x64 PIPE1 (8, 9 dense only: short sequences), 10 = 256x256 / 11 = 192x256 8-wave
-// ping-pong (dense only, N % 256 == 0)
-// variant + 100 * S (S = 2..4): the 4-wave tiles with split-K over S blocks per tile (splitk_join)
+// the dense kernel of the variant's row (gemm_variants.h), split over K by variant / 100
 template <bool F16, int EPI>
 void launch_variant(int variant, const GemmParams& p, hipStream_t s) {
-    const int S = variant / 100;
-    if (S > 1 && variant % 100 == 18) throw std::runtime_error("gemm: split-K is not built for the warp-specialized tile");
-    switch (variant % 100) {
-        case 0: launch_cfg<128, 128, 2, 2, F16, EPI, 0>(p, S, s); break;
-        case 1: launch_cfg<128, 128, 2, 2, F16, EPI, 1>(p, S, s); break;
-        case 2: launch_cfg<256, 256, 2, 4, F16, EPI, 1>(p, S, s); break;
-        case 3: launch_cfg<256, 128, 2, 2, F16, EPI, 1>(p, S, s); break;
-        case 4: launch_cfg<192, 128, 2, 2, F16, EPI, 1>(p, S, s); break;
-        case 5: launch_cfg<192, 256, 2, 4, F16, EPI, 1>(p, S, s); break;
-        case 6: launch_cfg<192, 64, 2, 2, F16, EPI, 1>(p, S, s); break;
-        case 7: launch_cfg<96, 128, 2, 2, F16, EPI, 1>(p, S, s); break;
-        case 8: launch_cfg<64, 128, 2, 2, F16, EPI, 1>(p, S, s); break;
-        case 9: launch_cfg<64, 64, 2, 2, F16, EPI, 1>(p, S, s); break;
-        case 10: launch_cfg8<256, F16, EPI>(p, S, s); break;
-        case 11: launch_cfg8<192, F16, EPI>(p, S, s); break;
-        case 12: launch_cfg<64, 64, 2, 2, F16, EPI, 4>(p, S, s); break;
-        case 13: launch_cfg<64, 128, 2, 2, F16, EPI, 3>(p, S, s); break;
-        case 14: launch_cfg<96, 128, 2, 2, F16, EPI, 3>(p, S, s); break;
-        case 15: launch_cfg<128, 128, 2, 2, F16, EPI, 3>(p, S, s); break;
-        // 8 waves (4 x 2) on a 192x128 tile: one tile per CU at M = 3000, N = 2048 (256 tiles), two waves per SIMD
-        case 16: launch_cfg<192, 128, 4, 2, F16, EPI, 1>(p, S, s); break;
-        // warp-specialized (4 MFMA + 4 loader waves) 192x128, three k-tiles in the ring (forced only: +18 % isolated at
-        // the K = 6144 down projection, neutral in the sampling loop; a 3-stage single-role 192x128 tile (0.7x) and a
-        // 4-slot ring (equal or slower) measured in round 4 are not built)
-        case 18: launch_ws<192, 128, F16, EPI, 3>(p, s); break;
-        default: throw std::runtime_error("gemm: bad variant");
-    }
+    const int S = check_variant_launch(variant, p.N, p.K, false);
+    with_variant_row(variant % 100, [&](auto row) {
+        constexpr GemmVariantRow r = GEMM_VARIANTS[decltype(row)::value];
+        constexpr GemmKernelSel k = r.dense;
+        if constexpr (k.family == GemmFamily::Tile) {
+            launch_cfg<k.bm, k.bn, k.wm, k.wn, F16, EPI, k.depth, (r.dense_split > 1)>(p, S, s);
+        } else if constexpr (k.family == GemmFamily::PingPong) {
+            static_assert(r.dense_split == 2 && SplitKMax<k.bm, 256>::value == 2, "the ping-pong tiles split K over two parts");
+            launch_cfg8<k.bm, F16, EPI>(p, S, s);
+        } else if constexpr (k.family == GemmFamily::WarpSpec) {
+            static_assert(r.dense_split == 1, "split-K is not built for the warp-specialized tile");
+            launch_ws<k.bm, k.bn, F16, EPI, k.depth>(p, s);
+        }  // (a row without a dense kernel: check_variant_launch has thrown)
+    });
 }
-
-template <bool F16>
-void dispatch_epi(int variant, const GemmParams& p, hipStream_t s) {
-    switch (p.e.kind) {
-        case EPI_STORE_F32: launch_variant<F16, EPI_STORE_F32>(variant, p, s); break;
-        case EPI_STORE_ACT: launch_variant<F16, EPI_STORE_ACT>(variant, p, s); break;
-        case EPI_RESID_GATED: launch_variant<F16, EPI_RESID_GATED>(variant, p, s); break;
-        case EPI_RESID: launch_variant<F16, EPI_RESID>(variant, p, s); break;
-        case EPI_SWIGLU: launch_variant<F16, EPI_SWIGLU>(variant, p, s); break;
-        case EPI_PROJ_OUT: launch_variant<F16, EPI_PROJ_OUT>(variant, p, s); break;
-        case EPI_QKV_PREP: launch_variant<F16, EPI_QKV_PREP>(variant, p, s); break;
-        default: throw std::runtime_error("gemm: bad epilogue kind");
-    }
-}
-
 
 }  // namespace gemm_detail
 
@@ -821,135 +784,12 @@ using namespace gemm_detail;
 
 int g_forced_variant = -1;
 
-// Tile choice: measured kernel ceiling (random bf16 operands, MI355X: v1 ~950, v2 ~1120 TFLOP/s at
-// large shapes) times the wave-quantization efficiency of the grid over 256 CUs (v1: 2 blocks/CU,
-// 64 KiB LDS each; v2: 1 block/CU, 128 KiB) and the M-edge utilisation.
-// Tile choice from the measured table (tools/gemm_bench.py on MI355X, profiles/r01_gemm_bench.log): at
-// M = 3000 the 192-row tiles make 16 exact M blocks, so 192x128 fills the chip in whole rounds where
-// 128x128 leaves a half round (qkv: 512 vs 768 tiles, 1036 vs 854 TFLOP/s; gate|up 1536 tiles, 900 vs
-// 827); with only N = 2048 (256 tiles) the 128x128 tile's two blocks per CU win (down 779 vs 684).
-// Dequant-fused: 192x256 (one block per CU, the dequant VALU spread over 8 waves) leads where it
-// gives at least one tile per CU (gate|up 655 vs 525, qkv 709 vs 502), else 192x128 (down 506 vs 437).
-// Dense N = 2048 at M = 3000: 96x128 makes 512 tiles, exactly two blocks per CU (down 857 vs 775,
-// o / cross 662 vs 569).
-double m_edge(int M, int bm) { return (double)M / (double)(((M + bm - 1) / bm) * bm); }
-
-// Quantized weights: the LDS-staged dequant kernel (gemm_qr_kernel, variants 20-24 [+ 100 S]); the round-1
-// ds_write dequant kernel (gemm_q_kernel, 0-7) only when forced.  Long sequences: 192-row tiles (8 waves where
-// N % 256 == 0 leaves a full round of 256-column tiles); short ones: 128 / 64-row tiles, split over K until
-// the grid covers the 256 CUs.
-int pick_variant_q(int M, int N, int K, int fmt) {
-    const int64_t mb192 = (M + 191) / 192;
-    (void)fmt;
-    if (M > 1024) {
-        // M = 3000 (tools/wsq_bench.py, profiles/r05/wsq/): gate|up / qkv on the 8-wave register-dequant tile (21),
-        // the N = 2048 projections on the warp-specialized tile (25: the expansion on loader waves; down 662 vs 539,
-        // o 560 vs 451 TFLOP/s for the 4-wave register-dequant tile)
-        if (N > 2048 && N % 256 == 0 && mb192 * (N / 256) >= 256) return 21;
-        return 25;
-    }
-    // Short sequences: round 1's LDS-dequant kernel (96 x 128).  Whole forwards through the 64 / 128-row
-    // register-dequant tiles (22, 23, split or not) were not run-to-run identical (tools/diag_det.py, round 3;
-    // every kernel-level test of them passes, the attention-prep epilogue is the one path those tests do not
-    // reach) -- forced only.
-    (void)K;
-    return 7;
-}
-
-// Per-shape overrides for in-loop A/B runs (ACE_MI_GEMM_OVERRIDE, read by the self-test library only:
-// runtime/test_hooks.cpp): the isolated-GEMM sweeps mispredicted the sampling loop at some shapes (cold weights,
-// fresh activations), so tile picks are confirmed with whole bench lines.
-static int gemm_override(int N, int K) { return gemm_override_from_env(N, K); }
-
+// The tile for a shape: gemm_variants.h (forced variant, per-shape override, else the measured rules).  The overrides are
+// for in-loop A/B runs (ACE_MI_GEMM_OVERRIDE, read by the self-test library only: runtime/test_hooks.cpp): the
+// isolated-GEMM sweeps mispredicted the sampling loop at some shapes (cold weights, fresh activations), so tile picks
+// are confirmed with whole bench lines.
 int pick_variant(int M, int N, int K, bool quant, int fmt) {
-    auto supports = [&](int v) {  // the tile / split-K factor handles this shape (and weight format)
-        const int f = v % 100, S = v / 100;
-        const bool wide = f == 2 || f == 5 || f == 10 || f == 11 || f == 21;  // (12-15: multi-stage rings)
-        const bool qr = f >= 20 && f <= 25;
-        const bool dense_only = (f == 6 || (f >= 8 && f < 20) || S > 1) && !qr;
-        const bool sk_ok = S <= 1 || (qr ? (f == 22 || f == 23) && S <= 4 && K / 64 >= 2 * S
-                                         : ((f == 1 || f == 3 || f == 4 || f == 10 || f == 11
-                                                 ? S <= 2
-                                                 : (((f >= 6 && f <= 9) || (f >= 12 && f <= 15)) && S <= 4)) &&
-                                            K / 64 >= 2 * S));
-        (void)fmt;
-        return !(wide && N % 256 != 0) && !(quant && dense_only) && !(!quant && qr) && sk_ok;
-    };
-    if (g_forced_variant >= 0x10000) return g_forced_variant & 0xffff;  // diagnostics (selftest): no support check
-    if (g_forced_variant >= 0 && supports(g_forced_variant)) return g_forced_variant;  // tests / micro-benchmarks
-    if (!quant) {
-        const int ov = gemm_override(N, K);
-        if (ov >= 0 && supports(ov)) return ov;
-    }
-    const int64_t mb192 = (M + 191) / 192;
-    const bool edge_ok = m_edge(M, 192) >= m_edge(M, 128) - 0.02;
-    if (quant) return pick_variant_q(M, N, K, fmt);
-    // (a skinny weight-stream kernel for M <= 128 ran the 10 s block linears 2x slower than the tiles below --
-    // every 16-column workgroup re-read all of A with 16-byte row-scattered loads -- and was removed in round 4)
-    // 8-wave ping-pong tiles for batched sequences (tools/gemm_msweep.py on MI355X, TFLOP/s): M = 12000 gate|up
-    // 1011 (256x256) vs 941 (v2), qkv 933 vs 902, down 922 (192x256) vs 818, o 814 vs 786; M = 24000 gate|up
-    // 1089 vs 1016, qkv 941 vs 897, down 955 vs 915, o 767 (v2) vs 724; M = 6000 down 921 (192x256) vs 853.
-    // At M = 3000 the 4-wave tiles stay ahead (their second block per CU hides prologue and epilogue).
-    // narrow outputs (proj_out: N = 128 at M = 3000 -- 16 tiles of 192 rows on a 256-CU chip, 28 TFLOP/s):
-    // 64x64 tiles (94 workgroups).  Not split over K: the summation order then stays the one every other tile
-    // (and the dequant-fused kernels) uses, which the staged == fused test relies on
-    if (N <= 128 && M >= 512) return 9;
-    // 600 s single sequences (M = 7500) and similar, 6800 <= M < 8192: the 256x256 ping-pong tiles (one round of
-    // 240 tiles for the N = 2048 projections) and the 8-wave 192x128 tiles for qkv.  Measured in the sampling loop
-    // (bench.py --seconds 600, same-box A/B against the previous picks, profiles/r03_pick_ab_600s/): 29.75 -> 33.25
-    // steps/s.  The isolated-GEMM sweep (profiles/r03_msweep_v16_*.jsonl) also favoured the 192x128 8-wave tiles at
-    // M = 4500..12000, but inside the loop (cold weights, fresh activations) they were neutral at M = 6000 and 2 %
-    // slower at M = 12000 (profiles/r03_bs_ab/), so the picks below 6800 and from 8192 stay as they were.
-    if (M >= 6800 && M < 8192) {
-        if (N <= 2048 && N % 256 == 0) return 10;
-        // qkv (N = 4096) on the 192x256 ping-pong tile with the fused prep: 26.94 steps/s at 600 s against 26.43-26.59
-        // for the 8-wave 192x128 tile (profiles/r05/pick_inloop_600s/); o / down / gate|up stay (192x256: 25.2 / 25.3 / 26.2)
-        if (N == 4096 && N % 256 == 0) return 11;
-        if (N <= 4096) return 16;
-        if (N % 256 == 0) return 10;
-    }
-    if (N % 256 == 0 && M >= 8192) {
-        if (N >= 4096) return 10;
-        // (M = 24000, eight 240 s items: o / cross q / cross o on the ping-pong 256x256 tile 83.7 item-steps/s against
-        //  80.9-81.0 for the 4-wave-family 256x256 and 82.9 for 192x256, profiles/r05/pick_inloop_bs8/)
-        if (M >= 20000) return 10;
-        return 11;
-    }
-    // two 240 s items (M = 6000): the ping-pong tiles, measured as whole bs = 2 lines through ACE_MI_GEMM_OVERRIDE
-    // (profiles/r05/pick_inloop_bs2/, item-steps/s): gate|up on 256x256 (1152 tiles, 4.5 rounds) 76.1 against 72.2-72.5
-    // for the 192x128 4-wave pick (192x256 75.3, 256x256 4-wave-family 73.8); then, with that pick, o / cross q / cross o
-    // (N = K = 2048, 256 tiles: one round) on 192x256 78.8 against 76.0-76.5 (256x256 76.9, 256x128 72.1) and qkv on
-    // 192x256 77.5 (256x256 75.9); the K = 6144 down projection stays on 192x256 (256x256 71.8, 8-wave 192x128 72.3)
-    if (N % 256 == 0 && M >= 5000 && M < 6800) return N >= 8192 ? 10 : 11;
-    if (N % 256 == 0 && M >= 4500 && N <= 2048 && K >= 4096) return 11;
-    if (edge_ok && mb192 * (N / 128) >= 384) return 4;
-    // short sequences (60 s: M = 750): too few 96-row tiles to cover the CUs -> 64-row tiles, and
-    // 64x64 when even those leave CUs idle (M = 750: N = 2048 projections 273-337 -> 364-453 TFLOP/s,
-    // qkv 519 -> 567, tools/gemm_small_m.py)
-    // split-K (tools/gemm_msweep.py, MI355X): only the K = 6144 down projection between the short and the
-    // full-length tiles gains (M = 1500: 96x128 over 2 parts 722 vs 637 TFLOP/s for 64x128); elsewhere the
-    // join's device-coherent partial round trip (~3-4 us after the main loop) costs more than the fuller grid
-    // (and at 60 s, M = 750: 163.4 steps/s against 158.5-159.4 for the 64x128 3-stage split-K pick,
-    //  profiles/r05/pick_inloop_60s/)
-    if (N <= 2048 && K >= 4096 && M >= 600 && M < 2000) return 207;
-    const int64_t mb96 = (M + 95) / 96, mb64 = (M + 63) / 64;
-    // Short sequences read every weight cold (each layer's weights were last touched one step earlier), so the
-    // picks below follow the cold-weight sweep (ACE_MI_BENCH_COLD=24, profiles/r03_msweep_cold_ns.jsonl), where
-    // the multi-stage rings keep more weight tiles in flight:
-    //  10 s (M = 125): gate|up 64x128 3-stage (296 vs 267 TFLOP/s for 64x64), qkv / o 64x64 4-stage (146 vs 114,
-    //  76 vs 74), the K = 6144 down 64x64 4-stage over 2 K parts (126 vs 69);
-    //  60 s (M = 750): qkv 96x128 (495 vs 433 for 64x128), down 64x128 3-stage over 2 K parts (387 vs 349)
-    if (M <= 256) {
-        if (K >= 4096) return 212;
-        return N >= 8192 ? 13 : 12;
-    }
-    if (K >= 4096 && mb96 * (N / 128) <= 256 && mb64 * (N / 128) < 256) return 213;
-    if (mb96 * (N / 128) <= 256) {
-        if (mb96 * (N / 128) == 256) return 7;  // one full round of 96-row tiles (60 s qkv)
-        return mb64 * (N / 128) >= 256 ? 8 : 9;
-    }
-    if (m_edge(M, 96) >= m_edge(M, 128) - 0.02) return 7;  // N = 2048: 512 tiles, two per CU
-    return 1;
+    return gemm_resolve_variant(g_forced_variant, gemm_override_from_env(N, K), M, N, K, quant, fmt);
 }
 
 }  // namespace
@@ -971,17 +811,18 @@ void launch_gemm(const uint16_t* A, int lda, const WeightView& W, int M, int N, 
         ACEMI_CHECK(epi.prep.q_col <= 0 && (epi.prep.k_col < 0 || epi.prep.k_col == 128 * nqc) &&
                         (epi.prep.v_col < 0 || epi.prep.v_col == 128 * (nqc + nkc)),
                     "gemm: fused attention prep expects the [q | k | v] head order");
-        if (v >= 100 && g_forced_variant < 0) v %= 100;  // (the narrow-output split-K pick is not for the prep)
-        v = v == 2 ? 3 : v == 5 ? 4 : v == 6 ? 1 : v == 9 ? 8 : v == 12 ? 13 : v;
+        v = gemm_prep_sibling(v, g_forced_variant >= 0);
     }
     switch (W.fmt) {
         case WF_BF16:
         case WF_F16:
             ACEMI_CHECK(W.ld % 8 == 0, "gemm: leading dims must be multiples of 8");
-            if (W.fmt == WF_F16)
-                dispatch_epi<true>(v, p, s);
-            else
-                dispatch_epi<false>(v, p, s);
+            with_epilogue_kind(epi.kind, [&](auto kind) {
+                if (W.fmt == WF_F16)
+                    launch_variant<true, decltype(kind)::value>(v, p, s);
+                else
+                    launch_variant<false, decltype(kind)::value>(v, p, s);
+            });
             break;
         case WF_Q8_0:
             ACEMI_CHECK(W.s != nullptr, "gemm: null scales");

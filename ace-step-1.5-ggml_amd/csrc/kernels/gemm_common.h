@@ -7,7 +7,10 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <stdexcept>
+#include <type_traits>
 
+#include "../gemm_variants.h"
 #include "../kernels.h"
 #include "prep_math.h"
 #include "mfma_guard.h"
@@ -567,6 +570,51 @@ __device__ __forceinline__ bool splitk_join(const GemmParams& p, f32x4 (&acc)[TM
             splitk_gather<TM, TN, NW, 4, SMEM>(acc, slot0, PER_TILE, part, smem, wid, lane);
     }
     return true;
+}
+
+// Host side: from run-time numbers to template arguments.
+// f(std::integral_constant<int, EPI>) for the epilogue kind of a launch_gemm call
+template <class F>
+void with_epilogue_kind(int kind, F&& f) {
+    switch (kind) {
+        case EPI_STORE_F32: f(std::integral_constant<int, EPI_STORE_F32>{}); break;
+        case EPI_STORE_ACT: f(std::integral_constant<int, EPI_STORE_ACT>{}); break;
+        case EPI_RESID_GATED: f(std::integral_constant<int, EPI_RESID_GATED>{}); break;
+        case EPI_RESID: f(std::integral_constant<int, EPI_RESID>{}); break;
+        case EPI_SWIGLU: f(std::integral_constant<int, EPI_SWIGLU>{}); break;
+        case EPI_PROJ_OUT: f(std::integral_constant<int, EPI_PROJ_OUT>{}); break;
+        case EPI_QKV_PREP: f(std::integral_constant<int, EPI_QKV_PREP>{}); break;
+        default: throw std::runtime_error("gemm: bad epilogue kind");
+    }
+}
+
+// f(std::integral_constant<int, I>) for the index I of base id `id` in GEMM_VARIANTS (gemm_variants.h): the launchers
+// take their template arguments from row I
+template <int I = 0, class F>
+void with_variant_row(int id, F&& f) {
+    if constexpr (I < GEMM_VARIANT_ROWS) {
+        if (GEMM_VARIANTS[I].id == id)
+            f(std::integral_constant<int, I>{});
+        else
+            with_variant_row<I + 1>(id, f);
+    } else {
+        throw std::runtime_error("gemm: bad variant");
+    }
+}
+
+// The checks of a variant against a shape, made once before the launch (a variant forced with the 0x10000 bit has
+// not been through gemm_variant_supports).  Returns the split-K factor.
+inline int check_variant_launch(int variant, int N, int K, bool quant) {
+    const int S = variant / 100;
+    const GemmVariantRow* r = variant >= 0 ? gemm_variant_row(variant % 100) : nullptr;
+    if (!r || (quant ? r->quant : r->dense).family == GemmFamily::None) throw std::runtime_error("gemm: bad variant");
+    if (N % (quant ? r->quant : r->dense).bn != 0) throw std::runtime_error("gemm: N is not a multiple of the tile's columns");
+    if (S > 1) {
+        if (S > (quant ? r->quant_split : r->dense_split))
+            throw std::runtime_error("gemm: split-K is not built for this tile, or not over that many parts");
+        if (K / 64 < 2 * S) throw std::runtime_error("gemm: split-K needs at least two K-tiles per part");
+    }
+    return S;
 }
 
 // split-K workspace for `ntiles` tiles of `tile_bytes` each, S parts, on stream s (gemm.hip)

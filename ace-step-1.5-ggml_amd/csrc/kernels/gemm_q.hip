@@ -841,7 +841,6 @@ __global__ void __launch_bounds__(512, 1) gemm_wsq_kernel(GemmParams p) {
 
 template <int BM, int BN, int EPI, int WQ, int NS>
 void launch_wsq_cfg(const GemmParams& p, hipStream_t s) {
-    if (p.N % BN != 0) throw std::runtime_error("gemm: the warp-specialized quantized tile needs N % 128 == 0");
     if constexpr (EPI == EPI_QKV_PREP && BN != 128) {
         throw std::runtime_error("gemm: the fused attention prep needs 128-wide column tiles");
     } else {
@@ -860,68 +859,48 @@ void launch_q_cfg(const GemmParams& p, hipStream_t s) {
         hipLaunchKernelGGL((gemm_q_kernel<BM, BN, WM, WN, EPI, WQ>), dim3(nbm * nbn), dim3(WM * WN * 64), 0, s, p);
 }
 
-// LDS-dequant kernel (gemm_qr_kernel): BM x (32 NW) tiles, split-K over S blocks per tile for the short ones
-template <int BM, int NW, int EPI, int WQ>
+// LDS-dequant kernel (gemm_qr_kernel): BM x (32 NW) tiles; SK: split-K over S blocks per tile (a row whose
+// quant_split > 1)
+template <int BM, int NW, int EPI, int WQ, bool SK>
 void launch_qr_cfg(GemmParams p, int S, hipStream_t s) {
+    static_assert(!SK || (BM <= 128 && NW == 4), "split-K is for the 64 / 128-row quantized tiles");
     constexpr int BN = 32 * NW;
-    if (p.N % BN != 0) throw std::runtime_error("gemm: quantized tile needs N % (32 * waves) == 0");
     const int nbm = (p.M + BM - 1) / BM;
     const int nbn = p.N / BN;
-    if (S > 1) {
-        if constexpr (BM <= 128 && NW == 4) {
-            if (p.K / 64 < 2 * S || S > 4) throw std::runtime_error("gemm: bad split-K factor");
+    if constexpr (SK) {
+        if (S > 1) {
             splitk_setup(p, nbm * nbn, S, (size_t)BM * BN * 4, s);
             hipLaunchKernelGGL((gemm_qr_kernel<BM, NW, EPI, WQ, true>), dim3(nbm * nbn * S), dim3(NW * 64), 0, s, p);
-        } else {
-            throw std::runtime_error("gemm: split-K is for the 64 / 128-row quantized tiles");
+            return;
         }
-    } else {
-        hipLaunchKernelGGL((gemm_qr_kernel<BM, NW, EPI, WQ>), dim3(nbm * nbn), dim3(NW * 64), 0, s, p);
     }
+    hipLaunchKernelGGL((gemm_qr_kernel<BM, NW, EPI, WQ>), dim3(nbm * nbn), dim3(NW * 64), 0, s, p);
 }
 
+// the quantized kernel of the variant's row (gemm_variants.h), split over K by variant / 100
 template <int EPI, int WQ>
 void launch_q_variant(int variant, const GemmParams& p, hipStream_t s) {
-    const int S = variant / 100;
-    switch (variant % 100) {
-        case 20: launch_qr_cfg<192, 4, EPI, WQ>(p, S, s); return;
-        case 21: launch_qr_cfg<192, 8, EPI, WQ>(p, S, s); return;
-        case 22: launch_qr_cfg<128, 4, EPI, WQ>(p, S, s); return;
-        case 23: launch_qr_cfg<64, 4, EPI, WQ>(p, S, s); return;
-        case 24: launch_qr_cfg<256, 4, EPI, WQ>(p, S, s); return;
-        case 25:
-            if (S > 1) throw std::runtime_error("gemm: no split-K for the warp-specialized quantized tile");
-            launch_wsq_cfg<192, 128, EPI, WQ, 3>(p, s);
-            return;
-        default: break;
-    }
-    if (S > 1) throw std::runtime_error("gemm: split-K is for the register-dequant tiles");
-    switch (variant) {
-        case 0:
-        case 1: launch_q_cfg<128, 128, 2, 2, EPI, WQ>(p, s); break;
-        case 2: launch_q_cfg<256, 256, 2, 4, EPI, WQ>(p, s); break;
-        case 3: launch_q_cfg<256, 128, 2, 2, EPI, WQ>(p, s); break;
-        case 4: launch_q_cfg<192, 128, 2, 2, EPI, WQ>(p, s); break;
-        case 5: launch_q_cfg<192, 256, 2, 4, EPI, WQ>(p, s); break;
-        case 7: launch_q_cfg<96, 128, 2, 2, EPI, WQ>(p, s); break;
-        default: throw std::runtime_error("gemm: bad variant");
-    }
+    const int S = check_variant_launch(variant, p.N, p.K, true);
+    with_variant_row(variant % 100, [&](auto row) {
+        constexpr GemmVariantRow r = GEMM_VARIANTS[decltype(row)::value];
+        constexpr GemmKernelSel k = r.quant;
+        if constexpr (k.family == GemmFamily::QTile) {
+            static_assert(r.quant_split == 1, "split-K is for the register-dequant tiles");
+            launch_q_cfg<k.bm, k.bn, k.wm, k.wn, EPI, WQ>(p, s);
+        } else if constexpr (k.family == GemmFamily::QRing) {
+            static_assert(r.quant_split <= 4, "the join gathers at most four parts");
+            launch_qr_cfg<k.bm, k.wn, EPI, WQ, (r.quant_split > 1)>(p, S, s);
+        } else if constexpr (k.family == GemmFamily::QWarpSpec) {
+            static_assert(r.quant_split == 1, "no split-K for the warp-specialized quantized tile");
+            launch_wsq_cfg<k.bm, k.bn, EPI, WQ, k.depth>(p, s);
+        }  // (a row without a quantized kernel: check_variant_launch has thrown)
+    });
 }
 
 template <int WQ>
 void dispatch_q_epi(int variant, const GemmParams& p, hipStream_t s) {
-    switch (p.e.kind) {
-        case EPI_STORE_F32: launch_q_variant<EPI_STORE_F32, WQ>(variant, p, s); break;
-        case EPI_STORE_ACT: launch_q_variant<EPI_STORE_ACT, WQ>(variant, p, s); break;
-        case EPI_RESID_GATED: launch_q_variant<EPI_RESID_GATED, WQ>(variant, p, s); break;
-        case EPI_RESID: launch_q_variant<EPI_RESID, WQ>(variant, p, s); break;
-        case EPI_SWIGLU: launch_q_variant<EPI_SWIGLU, WQ>(variant, p, s); break;
-        case EPI_PROJ_OUT: launch_q_variant<EPI_PROJ_OUT, WQ>(variant, p, s); break;
-        case EPI_QKV_PREP: launch_q_variant<EPI_QKV_PREP, WQ>(variant, p, s); break;
-        default: throw std::runtime_error("gemm: bad epilogue kind");
-    }
+    with_epilogue_kind(p.e.kind, [&](auto kind) { launch_q_variant<decltype(kind)::value, WQ>(variant, p, s); });
 }
-
 
 void dispatch_quant(int fmt, int variant, const GemmParams& p, hipStream_t s) {
     switch (fmt) {

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../../include/acestep_mi355x_selftest.h"
+#include "../gemm_variants.h"
 #include "../kernels.h"
 #include "quant.h"
 
@@ -410,8 +411,7 @@ ace_ggml_status ace_mi_kernel_gemm_q(int32_t qtype, int32_t epi, int32_t variant
     if (((epi == EPI_STORE_F32 || resid) && !out_f32) || (epi == EPI_SWIGLU && !out_u16))
         return ACE_GGML_ERR_INVALID_ARG;
     if (epi == EPI_RESID_GATED && !bias) return ACE_GGML_ERR_INVALID_ARG;
-    const int vb = variant >= 0 ? (variant & 0xffff) : variant;  // (0x10000: forced past the picker's support check)
-    if (variant < -1 || variant > 0x1ffff || vb % 100 > 25 || vb > 424) return ACE_GGML_ERR_INVALID_ARG;
+    if (!gemm_variant_arg_ok(variant, true)) return ACE_GGML_ERR_INVALID_ARG;  // (0x10000: past the support check)
     try {
         std::vector<uint8_t> qp(quant::q_plane_bytes(t, N, K));
         std::vector<float> sp(quant::s_plane_floats(t, N, K));
@@ -613,6 +613,40 @@ ace_ggml_status ace_mi_bench_gemm_q(int32_t qtype, int32_t epi, int32_t variant,
         return ACE_GGML_ERR;
     }
     return ACE_GGML_OK;
+}
+
+// The GEMM variant table and picker (csrc/gemm_variants.h) for the CPU tests: pure, no device.
+ace_ggml_status ace_mi_gemm_resolve(int32_t forced, int32_t override_v, int32_t M, int32_t N, int32_t K, int32_t wfmt,
+                                    int32_t prep, int32_t* variant) {
+    using namespace acemi;
+    if (!variant || M < 1 || N < 1 || K < 1) return ACE_GGML_ERR_INVALID_ARG;
+    const int v = gemm_resolve_variant(forced, override_v, M, N, K, weight_quantized(wfmt), wfmt);
+    *variant = prep ? gemm_prep_sibling(v, forced >= 0) : v;
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_gemm_variant_row(int32_t id, int32_t fields[16], char* name, size_t name_size) {
+    using namespace acemi;
+    const GemmVariantRow* r = gemm_variant_row(id);
+    if (!r || !fields) return ACE_GGML_ERR_INVALID_ARG;
+    const GemmKernelSel* ks[2] = {&r->dense, &r->quant};
+    for (int i = 0; i < 2; ++i) {
+        const int32_t f[6] = {(int32_t)ks[i]->family, ks[i]->bm, ks[i]->bn, ks[i]->wm, ks[i]->wn, ks[i]->depth};
+        std::copy(f, f + 6, fields + 6 * i);
+    }
+    fields[12] = r->dense_split;
+    fields[13] = r->quant_split;
+    fields[14] = r->prep_sibling;
+    fields[15] = r->dense.needs_n256() || r->quant.needs_n256();
+    if (name && name_size) {
+        std::strncpy(name, r->name, name_size - 1);
+        name[name_size - 1] = 0;
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_gemm_variant_arg_ok(int32_t variant, int32_t allow_unchecked) {
+    return acemi::gemm_variant_arg_ok(variant, allow_unchecked != 0) ? ACE_GGML_OK : ACE_GGML_ERR_INVALID_ARG;
 }
 
 }  // extern "C"

@@ -5,7 +5,7 @@
 //   ACE_MI_TEST_VAE_FAULT="block,row,col,amp"  adds amp to one 16 x 128 tile of the VAE decoder's residual stream
 //                                          after that block's first residual unit (tests/test_gpu_vae.py)
 //   ACE_MI_GEMM_OVERRIDE="N:K:variant,..." dense-weight GEMM tile picks per shape (in-loop A/B runs,
-//                                          tools/gpu_pick_inloop.sh)
+//                                          tools/gpu_pick_inloop.sh; the variant ids: gemm_variants.h)
 #include <array>
 #include <cstdio>
 #include <cstdlib>

@@ -2,6 +2,7 @@
 // encoders (quantize_row_*_ref restated, runtime/quant.cpp; used by the GGUF exporter and the tests) and the
 // GEMM tile override used for A/B measurements.
 #include "../../../include/acestep_mi355x.h"
+#include "../gemm_variants.h"
 #include "../kernels.h"
 #include "quant.h"
 
@@ -9,7 +10,7 @@ extern "C" {
 
 // Force a GEMM kernel variant for subsequent launches (-1 = automatic).
 ace_ggml_status ace_mi_gemm_variant(int32_t variant) {
-    if (variant < -1 || variant % 100 > 25 || variant > 424) return ACE_GGML_ERR_INVALID_ARG;
+    if (!acemi::gemm_variant_arg_ok(variant)) return ACE_GGML_ERR_INVALID_ARG;
     acemi::gemm_force_variant(variant);
     return ACE_GGML_OK;
 }

@@ -134,8 +134,10 @@ ACE_GGML_API ace_ggml_status ace_mi_probe_gemm(ace_ggml_context* ctx, int32_t wh
 /* Synchronise the context stream. */
 ACE_GGML_API ace_ggml_status ace_mi_synchronize(ace_ggml_context* ctx);
 
-/* Force the GEMM kernel variant of all later launches in this process (-1 = automatic; dense 0..11, quantized
- * 20..24, + 100 S for split-K over S blocks per tile; A/B measurements).  The kernel self-test and
+/* Force the GEMM kernel variant of all later launches in this process (-1 = automatic; the ids of
+ * csrc/gemm_variants.h: dense 0..16 and 18, quantized 0..5, 7 and 20..25, + 100 S for split-K over S = 2..4 blocks
+ * per tile where the row allows it; a variant that does not handle a launch's shape or weights is ignored for that
+ * launch; A/B measurements).  The kernel self-test and
  * micro-benchmark entries live in the separate test library (include/acestep_mi355x_selftest.h). */
 ACE_GGML_API ace_ggml_status ace_mi_gemm_variant(int32_t variant);
 

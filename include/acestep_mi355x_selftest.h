@@ -36,12 +36,14 @@ ACE_GGML_API ace_ggml_status ace_mi_bench_attention(int32_t B, int32_t Hq, int32
 
 /* GEMM micro-benchmark on random device operands: average ms per launch (HIP events) of the
  * engine's GEMM for act_type (0 bf16, 1 fp16), epilogue `epi` (0 f32 store, 2 gated residual,
- * 4 SwiGLU), kernel `variant` (-1 automatic, 0..9 forced: 128x128 two pipelines, 256x256, 256x128, 192x128, 192x256, 192x64, 96x128, 64x128, 64x64). */
+ * 4 SwiGLU), kernel `variant` (-1 automatic; forced: a dense id of csrc/gemm_variants.h, 0..16 or 18, + 100 S for
+ * split-K over S = 2..4 parts where the row allows it). */
 ACE_GGML_API ace_ggml_status ace_mi_bench_gemm(int32_t act_type, int32_t epi, int32_t variant, int32_t M, int32_t N,
                                                int32_t K, int32_t iters, float* avg_ms);
 /* Dequant-fused GEMM on ggml block rows W [N][K]: out = A . bf16(dequant(W))^T (+ bias), A bf16 [M][K];
- * epi 0 (f32 store) or 4 (SwiGLU, bf16 out [M][N/2]); variant -1 automatic, 0..7 forced (round 1's ds_write
- * dequant tiles; 6 and 8..11 are dense-only), 20..24 the LDS-DMA dequant tiles (+ 100 S: split-K). */
+ * epi 0 (f32 store) or 4 (SwiGLU, bf16 out [M][N/2]); variant -1 automatic; forced: a quantized id of
+ * csrc/gemm_variants.h -- 0..5 and 7 (round 1's ds_write dequant tiles), 20..24 (the LDS-staged dequant tiles; 22, 23
+ * + 100 S: split-K), 25 (warp-specialized); + 0x10000: launched without the picker's support check. */
 ACE_GGML_API ace_ggml_status ace_mi_kernel_gemm_q(int32_t qtype, int32_t epi, int32_t variant, int32_t M, int32_t N,
                                                   int32_t K, const uint16_t* A, const uint8_t* W_blocks,
                                                   const float* bias, float* out_f32, uint16_t* out_u16);
@@ -87,6 +89,21 @@ ACE_GGML_API ace_ggml_status ace_mi_kernel_lora_merge(int32_t fmt, int32_t total
 /* Dequant-fused GEMM micro-benchmark: average ms per launch (HIP events). */
 ACE_GGML_API ace_ggml_status ace_mi_bench_gemm_q(int32_t qtype, int32_t epi, int32_t variant, int32_t M, int32_t N,
                                                  int32_t K, int32_t iters, float* avg_ms);
+
+/* The GEMM variant table and picker (csrc/gemm_variants.h), without a device.
+ * ace_mi_gemm_resolve: the variant launch_gemm would launch for an M x N x K GEMM on weights of format wfmt (0 bf16,
+ * 1 fp16, 2 Q8_0, 3 Q4_K, 4 Q6_K) with `forced` as the forced variant (-1 none) and `override_v` as the per-shape
+ * override (-1 none); prep != 0: with the fused attention prep's sibling step.
+ * ace_mi_gemm_variant_row: the row of base id `id` (INVALID_ARG: no such row): fields = dense kernel {family, BM, BN,
+ * WM, WN, depth}, quantized kernel {the same six}, largest dense split-K factor, largest quantized one, prep sibling
+ * id, needs N % 256 == 0; family 0 none, 1 gemm_kernel, 2 gemm8_kernel, 3 gemm_ws_kernel, 4 gemm_q_kernel,
+ * 5 gemm_qr_kernel (WN = its waves), 6 gemm_wsq_kernel; the row's description into name (may be NULL).
+ * ace_mi_gemm_variant_arg_ok: OK if ace_mi_gemm_variant (allow_unchecked = 0) or the self-test entries
+ * (allow_unchecked = 1: the 0x10000 bit) accept `variant`. */
+ACE_GGML_API ace_ggml_status ace_mi_gemm_resolve(int32_t forced, int32_t override_v, int32_t M, int32_t N, int32_t K,
+                                                 int32_t wfmt, int32_t prep, int32_t* variant);
+ACE_GGML_API ace_ggml_status ace_mi_gemm_variant_row(int32_t id, int32_t fields[16], char* name, size_t name_size);
+ACE_GGML_API ace_ggml_status ace_mi_gemm_variant_arg_ok(int32_t variant, int32_t allow_unchecked);
 
 #ifdef __cplusplus
 }

@@ -237,9 +237,9 @@ def test_full_width_two_layers_240s(monkeypatch):
 
 
 def test_context_destroy_then_new_context_60s(monkeypatch):
-    """ADVICE r3: a context whose stream ran split-K GEMMs (the 60 s down projection, variant 213) is destroyed;
-    a forward in a new context on the same device must still run (no sync of the dead stream, no stale error
-    word) and give the same bits as the first context's forward."""
+    """a context whose stream ran split-K GEMMs (the 60 s down projection, variant 207: 96x128 tiles
+    over two K parts) is destroyed; a forward in a new context on the same device must still run (no sync of the dead
+    stream, no stale error word) and give the same bits as the first context's forward."""
     from acestep_mi355x.capi import GGMLCAPIBridge
     from acestep_mi355x.synthetic import cached_checkpoint, make_config
     d = cached_checkpoint(make_config(num_hidden_layers=2), seed=0, backend="torch")

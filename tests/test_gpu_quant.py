@@ -71,7 +71,7 @@ def test_gemm_q_matches_dequantized_product(qtype, variant, M, N, K):
 @pytest.mark.parametrize("variant", [-1, 1, 3, 4, 20, 22, 23, 24, 25])
 @pytest.mark.parametrize("M,K", [(1100, 128), (1100, 64), (300, 128)])
 def test_gemm_q_short_k_q8_0(variant, M, K):
-    """Q8_0 rows of K = 128 / 64 (four / two blocks): the warp-specialised tile (25, what pick_variant_q takes at
+    """Q8_0 rows of K = 128 / 64 (four / two blocks): the warp-specialised tile (25, what gemm_pick_auto_q takes at
     M > 1024 with N <= 2048 whatever K is) with only two / one k-tile in its 3-slot ring -- its prologue's counted wait
     (round 6 fix) -- and the other fused tiles' short pipelines."""
     capi = _capi()
