@@ -29,7 +29,7 @@ ACE_GGML_ERR_UNSUPPORTED = 4
 # Every symbol declared in include/acestep_ggml.h and include/acestep_mi355x.h.
 EXPORTED_SYMBOLS = (
     "ace_ggml_create", "ace_ggml_destroy", "ace_ggml_last_error", "ace_ggml_load_dit", "ace_ggml_dit_forward",
-    "ace_mi_create_on_device", "ace_mi_dit_get_info", "ace_mi_dit_forward_batched", "ace_mi_dit_sample",
+    "ace_mi_create_on_device", "ace_mi_dit_get_info", "ace_mi_dit_weight_desc", "ace_mi_dit_forward_batched", "ace_mi_dit_sample",
     "ace_mi_dit_sample_ex",
     "ace_mi_profile_enable", "ace_mi_dit_set_attn_precision", "ace_mi_profile_reset", "ace_mi_profile_get", "ace_mi_probe_gemm",
     "ace_mi_synchronize", "ace_mi_dit_load_lora", "ace_mi_dit_set_lora_scale", "ace_mi_dit_unload_lora",
@@ -49,10 +49,16 @@ EXPORTED_SYMBOLS = (
 SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_bench_attention", "ace_mi_bench_gemm",
                     "ace_mi_kernel_gemm_q", "ace_mi_kernel_dequant", "ace_mi_bench_gemm_q", "ace_mi_kernel_gemm_a8",
                     "ace_mi_kernel_gemm_a8_mode", "ace_mi_kernel_attn_kh", "ace_mi_kernel_lora_merge",
+                    "ace_mi_kernel_dequant_blocks", "ace_mi_kernel_dequant_segments", "ace_mi_bench_dequant_blocks",
                     "ace_mi_gemm_resolve", "ace_mi_gemm_variant_row", "ace_mi_gemm_variant_arg_ok")
 
 # qtype codes of ace_mi_quantize & co. (names as parse_quant_type, acestep_dit_model.cpp:27-37)
-QTYPES = {"q8_0": 1, "q4_k": 2, "q6_k": 3}
+QTYPES = {"q8_0": 1, "q4_k": 2, "q6_k": 3,
+          # decode-only (GGUF files carry them; dequantize and the raw-block kernels read them)
+          "q4_0": 4, "q4_1": 5, "q5_0": 6, "q5_1": 7, "q2_k": 8, "q3_k": 9, "q5_k": 10, "iq4_nl": 11}
+# ggml type ids of the block types (GGUF tensor type field; the raw-block kernels take these)
+GGML_BLOCK_TYPES = {"q4_0": 2, "q4_1": 3, "q5_0": 6, "q5_1": 7, "q8_0": 8, "q2_k": 10, "q3_k": 11, "q4_k": 12,
+                    "q5_k": 13, "q6_k": 14, "iq4_nl": 20}
 
 
 class AceInitParams(ctypes.Structure):
@@ -80,6 +86,11 @@ class AceMiLoraInfo(ctypes.Structure):
     _fields_ = [("loaded", ctypes.c_int32), ("scale", ctypes.c_float), ("lora_alpha", ctypes.c_float),
                 ("min_rank", ctypes.c_int32), ("max_rank", ctypes.c_int32), ("num_modules", ctypes.c_int32),
                 ("num_images", ctypes.c_int32), ("image_bytes", ctypes.c_int64), ("merge_ms", ctypes.c_double)]
+
+
+class AceMiBlockSeg(ctypes.Structure):
+    _fields_ = [("type", ctypes.c_int32), ("rows", ctypes.c_int32), ("row0", ctypes.c_int32), ("step", ctypes.c_int32),
+                ("group", ctypes.c_int32), ("blocks", ctypes.POINTER(ctypes.c_uint8))]
 
 
 class AceMiLoraJob(ctypes.Structure):
@@ -126,6 +137,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ace_ggml_dit_forward.restype = ctypes.c_int
     lib.ace_mi_dit_get_info.argtypes = [vp, ctypes.POINTER(AceMiDitInfo)]
     lib.ace_mi_dit_get_info.restype = ctypes.c_int
+    lib.ace_mi_dit_weight_desc.argtypes = [vp, ctypes.c_char_p, ctypes.c_size_t]
+    lib.ace_mi_dit_weight_desc.restype = ctypes.c_int
     lib.ace_mi_dit_forward_batched.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     lib.ace_mi_dit_forward_batched.restype = ctypes.c_int
     lib.ace_mi_dit_sample.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, fp, i32, vp]
@@ -269,6 +282,9 @@ def load_selftest_library() -> ctypes.CDLL:
     lib.ace_mi_kernel_attn_kh.restype = ctypes.c_int
     lib.ace_mi_kernel_lora_merge.argtypes = [i32, i32, i32, i32, i32, u16p, u16p, ctypes.POINTER(AceMiLoraJob), i32]
     lib.ace_mi_kernel_lora_merge.restype = ctypes.c_int
+    _bind_dequant_blocks(lib)
+    lib.ace_mi_bench_dequant_blocks.argtypes = [i32, i32, i32, i32, i32, fp]
+    lib.ace_mi_bench_dequant_blocks.restype = ctypes.c_int
     _bind_gemm_variants(lib)
     _SELFTEST = lib
     return lib
@@ -327,6 +343,12 @@ class GGMLCAPIBridge:
         info = AceMiDitInfo()
         self._ensure_ok(self.lib.ace_mi_dit_get_info(self.ctx, ctypes.byref(info)), "ace_mi_dit_get_info")
         self.info = info
+
+    def dit_weight_desc(self) -> str:
+        """The device formats of the loaded 2-D weights ("bf16", "q4_K planes", "ggml raw blocks (q5_K, q6_K)", ...)."""
+        buf = ctypes.create_string_buffer(256)
+        self._ensure_ok(self.lib.ace_mi_dit_weight_desc(self.ctx, buf, len(buf)), "ace_mi_dit_weight_desc")
+        return buf.value.decode("utf-8")
 
     def dit_forward_tfirst(self, hidden_states_tfirst, context_latents_tfirst, encoder_hidden_states_tfirst,
                            attention_mask, encoder_attention_mask, timestep: float, timestep_r: float) -> np.ndarray:
@@ -697,7 +719,9 @@ def bench_gemm(M: int, N: int, K: int, variant: int = -1, epi: int = 0, act_type
     return float(ms.value)
 
 
-_BLOCK = {"q8_0": (32, 34), "q4_k": (256, 144), "q6_k": (256, 210)}
+_BLOCK = {"q8_0": (32, 34), "q4_k": (256, 144), "q6_k": (256, 210), "q4_0": (32, 18), "q4_1": (32, 20),
+          "q5_0": (32, 22), "q5_1": (32, 24), "q2_k": (256, 84), "q3_k": (256, 110), "q5_k": (256, 176),
+          "iq4_nl": (32, 18)}
 
 
 def quantize(x: np.ndarray, qtype: str) -> np.ndarray:
@@ -739,6 +763,63 @@ def kernel_dequant(w_blocks: np.ndarray, qtype: str) -> np.ndarray:
     if st != ACE_GGML_OK:
         raise RuntimeError(f"ace_mi_kernel_dequant failed (status={st})")
     return out
+
+
+def _bind_dequant_blocks(lib):
+    i32 = ctypes.c_int32
+    u16p, u8p = ctypes.POINTER(ctypes.c_uint16), ctypes.POINTER(ctypes.c_uint8)
+    lib.ace_mi_kernel_dequant_blocks.argtypes = [i32, i32, i32, u8p, u16p]
+    lib.ace_mi_kernel_dequant_blocks.restype = ctypes.c_int
+    lib.ace_mi_kernel_dequant_segments.argtypes = [i32, ctypes.POINTER(AceMiBlockSeg), i32, i32, u16p]
+    lib.ace_mi_kernel_dequant_segments.restype = ctypes.c_int
+    return lib
+
+
+def kernel_dequant_blocks(blocks: np.ndarray, qtype: str, lib=None) -> np.ndarray:
+    """The raw-block expansion (launch_dequant_blocks) of one matrix: ggml block bytes [N][nb][bb] of any block type
+    -> bf16 words [N][K] of rne_bf16(ggml dequant).  `lib`: a loaded library that exports the entry (default: the GPU
+    self-test library)."""
+    lib = _bind_dequant_blocks(lib) if lib is not None else load_selftest_library()
+    w = np.ascontiguousarray(blocks, dtype=np.uint8)
+    N, nb = w.shape[0], w.shape[1]
+    K = nb * _BLOCK[qtype][0]
+    out = np.empty((N, K), dtype=np.uint16)
+    st = lib.ace_mi_kernel_dequant_blocks(GGML_BLOCK_TYPES[qtype], N, K, w.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)))
+    if st != ACE_GGML_OK:
+        raise RuntimeError(f"ace_mi_kernel_dequant_blocks failed (status={st})")
+    return out
+
+
+def kernel_dequant_segments(out_bits: np.ndarray, segs, lib=None) -> np.ndarray:
+    """launch_dequant_blocks on row segments, one call: out_bits uint16 [rows][K] = the initial content of the
+    destination; each segment a dict (qtype, blocks [n][nb][bb], row0, step = 1, group = 1): source row r lands at row
+    row0 + (r // group) * group * step + r % group.  Returns the destination after the launches."""
+    lib = _bind_dequant_blocks(lib) if lib is not None else load_selftest_library()
+    out = np.array(out_bits, dtype=np.uint16, order="C", copy=True)
+    keep = []
+    arr = (AceMiBlockSeg * len(segs))()
+    for i, g in enumerate(segs):
+        b = np.ascontiguousarray(g["blocks"], dtype=np.uint8)
+        keep.append(b)
+        arr[i] = AceMiBlockSeg(type=GGML_BLOCK_TYPES[g["qtype"]], rows=int(b.shape[0]), row0=int(g["row0"]),
+                               step=int(g.get("step", 1)), group=int(g.get("group", 1)),
+                               blocks=b.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    st = lib.ace_mi_kernel_dequant_segments(len(segs), arr, out.shape[0], out.shape[1],
+                                            out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16)))
+    if st != ACE_GGML_OK:
+        raise RuntimeError(f"ace_mi_kernel_dequant_segments failed (status={st})")
+    return out
+
+
+def bench_dequant_blocks(qtype: str, N: int, K: int, iters: int = 20, planes: bool = False) -> float:
+    """Average ms of one [N][K] expansion: the raw-block kernel, or (planes) the plane kernel on the same blocks."""
+    lib = load_selftest_library()
+    ms = ctypes.c_float(0.0)
+    st = lib.ace_mi_bench_dequant_blocks(GGML_BLOCK_TYPES[qtype], 1 if planes else 0, N, K, iters, ctypes.byref(ms))
+    if st != ACE_GGML_OK:
+        raise RuntimeError(f"ace_mi_bench_dequant_blocks failed (status={st})")
+    return float(ms.value)
 
 
 LORA_ROWS_PLAIN, LORA_ROWS_INTERLEAVE = 0, 1

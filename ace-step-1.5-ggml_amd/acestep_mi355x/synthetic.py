@@ -335,7 +335,8 @@ def write_vae_checkpoint(out_dir: str, cfg: dict, seed: int = 0, dtype: str = "F
 
 
 # ----------------------------------------------------------------------------- GGUF export
-GGML_TYPES = {"F32": 0, "F16": 1, "Q8_0": 8, "Q4_K": 12, "Q6_K": 14, "BF16": 30}
+GGML_TYPES = {"F32": 0, "F16": 1, "Q4_0": 2, "Q4_1": 3, "Q5_0": 6, "Q5_1": 7, "Q8_0": 8, "Q2_K": 10, "Q3_K": 11,
+              "Q4_K": 12, "Q5_K": 13, "Q6_K": 14, "IQ4_NL": 20, "BF16": 30}
 _QUANT_ARG = {"F16": None, "Q8": "Q8_0", "Q8_0": "Q8_0", "Q6": "Q6_K", "Q6_K": "Q6_K", "Q4": "Q4_K", "Q4_K": "Q4_K"}
 _QBLOCK = {"Q8_0": 32, "Q4_K": 256, "Q6_K": 256}
 
@@ -383,6 +384,12 @@ def write_gguf(safetensors_path: str, out_path: str, quant: str = "Q8", arch: st
         else:
             entries.append((name, v.shape, GGML_TYPES["F16"], v.astype("<f2").tobytes()))
 
+    return _write_gguf_entries(entries, out_path, arch)
+
+
+def _write_gguf_entries(entries, out_path: str, arch: str = "acestep") -> str:
+    """GGUF v3, alignment 32: entries (name, numpy shape, ggml type id, data bytes); the shape is reversed into ggml
+    ne order."""
     def s(x: str) -> bytes:
         b = x.encode("utf-8")
         return struct.pack("<Q", len(b)) + b
@@ -409,6 +416,84 @@ def write_gguf(safetensors_path: str, out_path: str, quant: str = "Q8", arch: st
             f.write(b"\0" * ((32 - len(data) % 32) % 32))
     os.replace(tmp, out_path)
     return out_path
+
+
+# ggml block types: values per block, bytes per block, byte offsets of the fp16 fields (ggml-common.h block_* structs)
+GGML_BLOCKS = {
+    "Q4_0": (32, 18, (0,)), "Q4_1": (32, 20, (0, 2)), "Q5_0": (32, 22, (0,)), "Q5_1": (32, 24, (0, 2)),
+    "Q8_0": (32, 34, (0,)), "Q2_K": (256, 84, (80, 82)), "Q3_K": (256, 110, (108,)), "Q4_K": (256, 144, (0, 2)),
+    "Q5_K": (256, 176, (0, 2)), "Q6_K": (256, 210, (208,)), "IQ4_NL": (32, 18, (0,)),
+}
+# (scale, min as a multiple of the scale) that give dequantized values of std ~ 0.02, roughly centred, for uniformly
+# random code bytes; the second is 0 for types without a min field
+_RANDOM_BLOCK_SCALES = {
+    "Q4_0": (0.0043, 0.0), "Q4_1": (0.0043, -7.5), "Q5_0": (0.0022, 0.0), "Q5_1": (0.0022, -15.5),
+    "Q8_0": (0.00027, 0.0), "IQ4_NL": (0.00029, 0.0), "Q2_K": (0.0024, 1.5), "Q3_K": (0.0005, 0.0),
+    "Q4_K": (0.00012, 7.5), "Q5_K": (0.00006, 15.5), "Q6_K": (0.000015, 0.0),
+}
+
+
+def random_blocks(gtype: str, rows: int, cols: int, rng: np.random.Generator) -> np.ndarray:
+    """Valid random ggml blocks uint8 [rows][cols / block][block bytes]: uniformly random code bytes, every fp16 field
+    overwritten by a finite value sized so that the dequantized weights have std ~ 0.02.  Not an encoder: nothing
+    is fitted to any values."""
+    bv, bb, fields = GGML_BLOCKS[gtype]
+    assert cols % bv == 0, (gtype, cols)
+    nb = cols // bv
+    blk = rng.integers(0, 256, size=(rows, nb, bb), dtype=np.uint8)
+    scale, min_mult = _RANDOM_BLOCK_SCALES[gtype]
+    d = (scale * (0.5 + rng.random(size=(rows, nb)))).astype(np.float32)
+    if min_mult == 0.0:  # symmetric types: either sign
+        d = d * np.where(rng.random(size=(rows, nb)) < 0.5, -1.0, 1.0).astype(np.float32)
+    vals = [d] + ([d * np.float32(min_mult) * (0.9 + 0.2 * rng.random(size=(rows, nb))).astype(np.float32)]
+                  if len(fields) > 1 else [])
+    for off, v in zip(fields, vals):
+        h = v.astype("<f2")
+        assert np.all(np.isfinite(h.astype(np.float32)))
+        blk[:, :, off:off + 2] = h.view(np.uint8).reshape(rows, nb, 2)
+    return blk
+
+
+def q5_k_m_types(name: str, shape) -> Optional[str]:
+    """The type layout of a llama.cpp-style Q5_K_M file: Q5_K, with v_proj and down_proj in Q6_K."""
+    return "Q6_K" if ("v_proj" in name or "down_proj" in name) else "Q5_K"
+
+
+def write_gguf_typed(safetensors_path: str, out_path: str, types, seed: int = 0, arch: str = "acestep"):
+    """GGUF export with a type per tensor: `types` is a dict name -> type name or a callable (name, shape) -> type
+    name (None / a missing name: the tensor is stored F16), consulted for float tensors with >= 2 dims whose last
+    dim is a multiple of the type's block.  Q8_0 / Q4_K / Q6_K blocks come from this library's encoders like
+    write_gguf's; the decode-only types (Q4_0, Q4_1, Q5_0, Q5_1, Q2_K, Q3_K, Q5_K, IQ4_NL) get random_blocks -- valid
+    blocks that do not approximate the checkpoint's values; BF16 / F16 / F32 store the values.  Returns the entries
+    {name: (numpy shape, type name, data bytes)}."""
+    from . import capi
+    tensors = _read_safetensors_f32(safetensors_path)
+    rng = np.random.default_rng(seed)
+    entries, out = [], {}
+    for name, v in tensors.items():
+        t = types(name, v.shape) if callable(types) else types.get(name)
+        if t is not None and v.ndim >= 2 and t in GGML_BLOCKS and v.shape[-1] % GGML_BLOCKS[t][0] == 0:
+            rows = int(np.prod(v.shape[:-1]))
+            if t in _QBLOCK:
+                data = capi.quantize(v.reshape(rows, v.shape[-1]), t.lower()).tobytes()
+            else:
+                data = random_blocks(t, rows, v.shape[-1], rng).tobytes()
+        elif t == "BF16":
+            u = np.ascontiguousarray(v, dtype=np.float32).view(np.uint32)
+            data = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype("<u2").tobytes()
+        elif t == "F32":
+            data = v.astype("<f4").tobytes()
+        else:
+            t, data = "F16", v.astype("<f2").tobytes()
+        entries.append((name, v.shape, GGML_TYPES[t], data))
+        out[name] = (tuple(v.shape), t, data)
+    _write_gguf_entries(entries, out_path, arch)
+    return out
+
+
+def write_gguf_tensors(out_path: str, tensors, arch: str = "acestep") -> str:
+    """A GGUF file of ready-made tensors {name: (numpy shape, type name, data bytes)}."""
+    return _write_gguf_entries([(n, sh, GGML_TYPES[t], data) for n, (sh, t, data) in tensors.items()], out_path, arch)
 
 
 # ----------------------------------------------------------------------------- PEFT LoRA adapters

@@ -72,15 +72,24 @@ struct GemmEpilogue {
 // activation (`Q -> bf16 dequant-fused` MFMA GEMM).
 // WF_F32X3: an F32 weight as the fp16 triple [hi | lo | hi] along K (ld = 3K), multiplied with an
 // activation written as [hi | hi | lo] (Ah.Wh + Ah.Wl + Al.Wh) by the plain fp16 GEMM over 3K.
-enum WeightFormat : int { WF_BF16 = 0, WF_F16 = 1, WF_Q8_0 = 2, WF_Q4_K = 3, WF_Q6_K = 4, WF_F32X3 = 5 };
+// WF_GGML_RAW: raw ggml block rows exactly as the GGUF file holds them, as a list of row segments (BlockSeg below),
+// each with its own ggml type.  No GEMM reads this format: launch_dequant_blocks expands it to the dense bf16 image
+// first (the staged-dequant scopes of runtime/engine.h), and a bf16 activation multiplies that image.
+enum WeightFormat : int {
+    WF_BF16 = 0, WF_F16 = 1, WF_Q8_0 = 2, WF_Q4_K = 3, WF_Q6_K = 4, WF_F32X3 = 5, WF_GGML_RAW = 6
+};
+struct BlockSeg;
 struct WeightView {
     int fmt = WF_BF16;
-    const void* q = nullptr;   // dense uint16 [N][ld] | Q8_0/Q6_K int8 [N][K] | Q4_K u8 [N][K/2]
+    const void* q = nullptr;   // dense uint16 [N][ld] | Q8_0/Q6_K int8 [N][K] | Q4_K u8 [N][K/2] | raw: the blocks
     const float* s = nullptr;  // Q8_0 [N][K/32] | Q4_K [N][K/32][2] (d*sc, dmin*m) | Q6_K [N][K/16]
     int ld = 0;                // dense leading dimension (elements)
+    const BlockSeg* segs = nullptr;  // WF_GGML_RAW: the matrix's row segments (host array owned by the DevWeight)
+    int n_segs = 0;
 };
 inline ActType weight_act(int fmt) { return (fmt == WF_F16 || fmt == WF_F32X3) ? ActType::F16 : ActType::BF16; }
 inline bool weight_quantized(int fmt) { return fmt >= WF_Q8_0; }
+inline bool weight_planes(int fmt) { return fmt == WF_Q8_0 || fmt == WF_Q4_K || fmt == WF_Q6_K; }
 
 void launch_gemm(const uint16_t* A, int lda, const WeightView& W, int M, int N, int K, const GemmEpilogue& epi,
                  hipStream_t s);
@@ -104,6 +113,32 @@ struct DequantJob {
     uint16_t* out = nullptr;
 };
 void launch_dequant_bf16_batch(const DequantJob* jobs, int n, hipStream_t s);
+
+// ------------------------------------------------- raw ggml blocks -> bf16 image (kernels/dequant_blocks.hip)
+// One run of `rows` consecutive block rows of one ggml type (runtime/gguf.h ids: Q4_0, Q4_1, Q5_0, Q5_1, Q8_0, Q2_K,
+// Q3_K, Q4_K, Q5_K, Q6_K, IQ4_NL), source row r at src + r * row_bytes, expanded to output row
+//   row0 + (r / group) * group * step + r % group
+// of a dense bf16 matrix [.][ld] with K values per row: step 1 = a concatenated part starting at row0; step 2 with
+// group 16 and row0 = 0 / 16 = the gate / up rows of the interleaved w_gu.  Every value is rne_bf16 of ggml's CPU
+// dequantize_row_* f32 value (runtime/quant.h) -- for Q8_0 / Q4_K / Q6_K the bits of launch_dequant_bf16 on the same
+// blocks, whose zeros are always +0.  src is 16-byte aligned and readable up to the next 16-byte boundary
+// after its last block (the kernel stages whole aligned 16-byte words); out is 16-byte aligned, K % 8 == 0 beyond
+// K % block == 0, ld % 8 == 0.
+struct BlockSeg {
+    int type = 0;            // ggml type id
+    const void* src = nullptr;
+    int rows = 0;
+    int row0 = 0, step = 1, group = 1;
+};
+inline int block_seg_row(const BlockSeg& g, int r) { return g.row0 + (r / g.group) * g.group * g.step + r % g.group; }
+struct DequantBlocksJob {
+    BlockSeg seg;
+    int K = 0;
+    int64_t ld = 0;
+    uint16_t* out = nullptr;
+};
+// any number of jobs: grouped by type, up to 8 jobs per launch; jobs of one call must not write the same rows
+void launch_dequant_blocks(const DequantBlocksJob* jobs, int n, hipStream_t s);
 
 // ------------------------------------------------- LoRA merge (kernels/lora.hip)
 // The adapted 16-bit image of a (possibly fused) weight matrix: for module row o and column i

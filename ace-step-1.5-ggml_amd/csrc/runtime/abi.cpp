@@ -192,6 +192,14 @@ ace_ggml_status ace_mi_dit_get_info(ace_ggml_context* ctx, ace_mi_dit_info* out)
     return ACE_GGML_OK;
 }
 
+ace_ggml_status ace_mi_dit_weight_desc(ace_ggml_context* ctx, char* buf, size_t buf_size) {
+    if (!ctx || !buf || buf_size == 0) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->dit) return set_error(ctx, ACE_GGML_ERR, "dit not loaded");
+    const std::string d = acemi::describe_weights(ctx->dit->model());
+    std::snprintf(buf, buf_size, "%s", d.c_str());
+    return ACE_GGML_OK;
+}
+
 ace_ggml_status ace_mi_dit_forward_batched(ace_ggml_context* ctx, int32_t batch, const float* d_hidden,
                                            const float* d_context, const float* d_enc, const int32_t* d_mask,
                                            const int32_t* d_enc_mask, int32_t seq_len, int32_t enc_len,

@@ -65,7 +65,41 @@ DitEngine::~DitEngine() {
 
 namespace {
 size_t wbytes(const DevWeight& w) { return (size_t)w.rows * w.cols * 2; }
+
+// The bf16 images of quantized matrices: plane formats through launch_dequant_bf16_batch (one launch per format),
+// raw-block matrices through launch_dequant_blocks (one job per row segment, one launch per ggml type).
+struct Expander {
+    DequantJob planes[8];
+    int n_planes = 0;
+    std::vector<DequantBlocksJob> blocks;
+    void add(const WeightView& v, int rows, int cols, uint16_t* out, hipStream_t s) {
+        if (v.fmt == WF_GGML_RAW) {
+            for (int i = 0; i < v.n_segs; ++i) blocks.push_back(DequantBlocksJob{v.segs[i], cols, cols, out});
+            return;
+        }
+        if (n_planes == 8 || (n_planes > 0 && v.fmt != planes[0].w.fmt)) flush_planes(s);
+        planes[n_planes++] = DequantJob{v, rows, cols, out};
+    }
+    void flush_planes(hipStream_t s) {
+        if (n_planes > 0) launch_dequant_bf16_batch(planes, n_planes, s);
+        n_planes = 0;
+    }
+    void flush(hipStream_t s) {
+        flush_planes(s);
+        if (!blocks.empty()) launch_dequant_blocks(blocks.data(), (int)blocks.size(), s);
+        blocks.clear();
+    }
+};
+void expand_weight(const WeightView& v, int rows, int cols, uint16_t* out, hipStream_t s) {
+    Expander e;
+    e.add(v, rows, cols, out, s);
+    e.flush(s);
+}
 }  // namespace
+
+// Whether the layer loop multiplies the staged bf16 image of a matrix of this format: every quantized format by
+// default; with ACE_MI_QUANT_STAGED=0 only raw ggml blocks, which no dequant-fused GEMM reads.
+bool DitEngine::stages(int fmt) const { return staged_quant_ ? weight_quantized(fmt) : fmt == WF_GGML_RAW; }
 
 // The six block matrices of layer li: views of the bf16 staging slot (staged) or of the resident weights.
 DitEngine::LayerViews DitEngine::layer_views(int li, bool staged) {
@@ -77,7 +111,7 @@ DitEngine::LayerViews DitEngine::layer_views(int li, bool staged) {
     for (int i = 0; i < 6; ++i) {
         v[i] = ws[i]->view();
         if (lora_view(*ws[i], v[i])) {  // the adapted image in place of the resident / staged weights
-        } else if (staged && weight_quantized(ws[i]->fmt)) {
+        } else if (staged && stages(ws[i]->fmt)) {
             v[i].fmt = WF_BF16;
             v[i].q = base + off;
             v[i].s = nullptr;
@@ -93,21 +127,15 @@ void DitEngine::stage_layer(int li, hipStream_t st) {
     const DevWeight* ws[6] = {&ly.w_qkv, &ly.w_o, &ly.w_cq, &ly.w_co, &ly.w_gu, &ly.w_down};
     char* base = stage_slot(li);
     size_t off = 0;
-    DequantJob jobs[6];
-    int n = 0;
+    Expander ex;
+    tic(st);
     for (int i = 0; i < 6; ++i) {
         WeightView adapted;
-        if (weight_quantized(ws[i]->fmt) && ws[i]->q && !lora_view(*ws[i], adapted)) {  // (adapted: never read)
-            if (n > 0 && ws[i]->fmt != jobs[0].w.fmt) {  // one launch per weight format
-                launch_dequant_bf16_batch(jobs, n, st);
-                n = 0;
-            }
-            jobs[n++] = DequantJob{ws[i]->view(), ws[i]->rows, ws[i]->cols, reinterpret_cast<uint16_t*>(base + off)};
-        }
+        if (stages(ws[i]->fmt) && ws[i]->q && !lora_view(*ws[i], adapted))  // (adapted: never read)
+            ex.add(ws[i]->view(), ws[i]->rows, ws[i]->cols, reinterpret_cast<uint16_t*>(base + off), st);
         off += wbytes(*ws[i]);
     }
-    tic(st);
-    if (n > 0) launch_dequant_bf16_batch(jobs, n, st);
+    ex.flush(st);
     toc("dequant_stage", st);
     images_written_ = true;
 }
@@ -115,11 +143,13 @@ void DitEngine::stage_layer(int li, hipStream_t st) {
 WeightView DitEngine::dense_view(const DevWeight& w, hipStream_t s) {
     WeightView v = w.view();
     if (lora_view(w, v)) return v;
-    if (!staged_quant_ || !stage_per_call_ || !weight_quantized(v.fmt) || !v.q) return v;
+    // (a raw-block matrix always gets its image, in every scope: no GEMM reads the blocks)
+    if (v.fmt != WF_GGML_RAW && (!staged_quant_ || !stage_per_call_ || !weight_quantized(v.fmt))) return v;
+    if (!v.q) return v;
     Buf& b = img_[v.q];
     if (!b.p) {
         ensure(b, (size_t)w.rows * w.cols * 2);
-        launch_dequant_bf16(v, w.rows, w.cols, static_cast<uint16_t*>(b.p), s);
+        expand_weight(v, w.rows, w.cols, static_cast<uint16_t*>(b.p), s);
         images_written_ = true;
     }
     v.fmt = WF_BF16;
@@ -480,7 +510,14 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
 
     // staged dequant (product): each layer's quantized block matrices are expanded to their bf16 image right before
     // the layer, in stream order, into one workspace slot (see engine.h)
-    const bool staged = !QACT && staged_quant_ && n_layers > 0 && weight_quantized(m.layers[0].w_gu.fmt);
+    bool any_raw = false;  // (raw blocks are staged whatever ACE_MI_QUANT_STAGED says: stages())
+    for (int li = 0; li < n_layers; ++li) {
+        const DevLayer& ly = m.layers[li];
+        for (const DevWeight* w : {&ly.w_qkv, &ly.w_o, &ly.w_cq, &ly.w_co, &ly.w_gu, &ly.w_down})
+            any_raw = any_raw || w->fmt == WF_GGML_RAW;
+    }
+    const bool staged =
+        !QACT && n_layers > 0 && ((staged_quant_ && weight_quantized(m.layers[0].w_gu.fmt)) || any_raw);
     bool restage = true;
     if (staged) {
         const DevLayer& l0 = m.layers[0];
@@ -828,7 +865,7 @@ void DitEngine::rebuild_lora_images(hipStream_t s) {
     ACEMI_HIP(hipDeviceSynchronize());
     const auto t0 = std::chrono::steady_clock::now();
     for (const DevWeight* w : expand)
-        launch_dequant_bf16(w->view(), w->rows, w->cols, static_cast<uint16_t*>(lora_img_[w->q].p), s);
+        expand_weight(w->view(), w->rows, w->cols, static_cast<uint16_t*>(lora_img_[w->q].p), s);
     launch_lora_merge(jobs.data(), (int)jobs.size(), s);
     ACEMI_HIP(hipStreamSynchronize(s));
     lora_merge_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

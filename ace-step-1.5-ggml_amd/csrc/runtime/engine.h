@@ -213,6 +213,7 @@ class DitEngine {
     bool stage_ev_set_ = false;
     bool images_written_ = false;
     WeightView dense_view(const DevWeight& w, hipStream_t s);
+    bool stages(int fmt) const;  // the layer loop reads this format's staged image (raw ggml blocks: always)
     char* stage_slot(int li);
     LayerViews layer_views(int li, bool staged);
     void stage_layer(int li, hipStream_t st);

@@ -78,28 +78,55 @@ struct Reader {
 
 }  // namespace
 
+namespace {
+struct BlockType {
+    int type, values, bytes;
+    const char* name;
+};
+// ggml type id, values per block, bytes per block (ggml-common.h block_* structs)
+constexpr BlockType kBlockTypes[] = {
+    {GGML_Q4_0, 32, 18, "q4_0"},  {GGML_Q4_1, 32, 20, "q4_1"},   {GGML_Q5_0, 32, 22, "q5_0"},
+    {GGML_Q5_1, 32, 24, "q5_1"},  {GGML_Q8_0, 32, 34, "q8_0"},   {GGML_Q2_K, 256, 84, "q2_K"},
+    {GGML_Q3_K, 256, 110, "q3_K"}, {GGML_Q4_K, 256, 144, "q4_K"}, {GGML_Q5_K, 256, 176, "q5_K"},
+    {GGML_Q6_K, 256, 210, "q6_K"}, {GGML_IQ4_NL, 32, 18, "iq4_nl"},
+};
+const BlockType* block_type(int type) {
+    for (const BlockType& b : kBlockTypes)
+        if (b.type == type) return &b;
+    return nullptr;
+}
+}  // namespace
+
+int ggml_block_values(int type) {
+    const BlockType* b = block_type(type);
+    return b ? b->values : 0;
+}
+int ggml_block_bytes(int type) {
+    const BlockType* b = block_type(type);
+    return b ? b->bytes : 0;
+}
+
 uint64_t ggml_row_bytes(int type, int64_t ne0) {
     switch (type) {
         case GGML_F32: return (uint64_t)ne0 * 4;
         case GGML_F16:
         case GGML_BF16: return (uint64_t)ne0 * 2;
-        case GGML_Q8_0: return ne0 % 32 ? 0 : (uint64_t)(ne0 / 32) * 34;
-        case GGML_Q4_K: return ne0 % 256 ? 0 : (uint64_t)(ne0 / 256) * 144;
-        case GGML_Q6_K: return ne0 % 256 ? 0 : (uint64_t)(ne0 / 256) * 210;
-        default: return 0;
+        default: break;
     }
+    const BlockType* b = block_type(type);
+    if (!b || ne0 % b->values) return 0;
+    return (uint64_t)(ne0 / b->values) * b->bytes;
 }
 
-const char* ggml_type_name(int type) {
+std::string ggml_type_name(int type) {
     switch (type) {
         case GGML_F32: return "f32";
         case GGML_F16: return "f16";
         case GGML_BF16: return "bf16";
-        case GGML_Q8_0: return "q8_0";
-        case GGML_Q4_K: return "q4_K";
-        case GGML_Q6_K: return "q6_K";
-        default: return "unsupported";
+        default: break;
     }
+    const BlockType* b = block_type(type);
+    return b ? std::string(b->name) : "type " + std::to_string(type);
 }
 
 void GgufFile::open(const std::string& p) {
@@ -142,7 +169,7 @@ void GgufFile::open(const std::string& p) {
         t.offset = r.get<uint64_t>();
         for (size_t d = 1; d < t.ne.size(); ++d) n *= t.ne[d];
         const uint64_t rb = ggml_row_bytes(t.type, t.ne_at(0));
-        t.nbytes = rb * (uint64_t)n;  // 0 for unsupported types: rejected at use
+        t.nbytes = rb * (uint64_t)n;  // 0 for unsupported types / row lengths: rejected at use
         list.push_back(t);
     }
     const uint64_t pos = (uint64_t)r.in.tellg();
@@ -156,6 +183,15 @@ void GgufFile::open(const std::string& p) {
     }
 }
 
+// why a tensor cannot be read: a ggml type outside the table (its numeric id), or a row that is no whole number of blocks
+std::string gguf_unsupported(const GgufTensor& t) {
+    const int bv = ggml_block_values(t.type);
+    if (bv && t.ne_at(0) % bv)
+        return "gguf tensor " + t.name + ": row length " + std::to_string(t.ne_at(0)) + " is not a multiple of the " +
+               ggml_type_name(t.type) + " block (" + std::to_string(bv) + ")";
+    return "unsupported gguf tensor type " + std::to_string(t.type) + " (ggml type id): " + t.name;
+}
+
 const GgufTensor& GgufFile::get(const std::string& n) const {
     auto it = tensors.find(n);
     if (it == tensors.end()) throw std::runtime_error("missing tensor in gguf: " + n);
@@ -163,7 +199,7 @@ const GgufTensor& GgufFile::get(const std::string& n) const {
 }
 
 std::vector<uint8_t> GgufFile::read(const GgufTensor& t) const {
-    if (!t.nbytes) throw std::runtime_error(std::string("unsupported gguf tensor type ") + ggml_type_name(t.type) + ": " + t.name);
+    if (!t.nbytes) throw std::runtime_error(gguf_unsupported(t));
     std::vector<uint8_t> buf(t.nbytes);
     std::ifstream in(path, std::ios::binary);
     in.seekg((std::streamoff)(data_offset + t.offset));

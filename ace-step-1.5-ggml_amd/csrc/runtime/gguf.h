@@ -18,9 +18,17 @@ namespace acemi {
 enum GgmlType : int {
     GGML_F32 = 0,
     GGML_F16 = 1,
+    GGML_Q4_0 = 2,
+    GGML_Q4_1 = 3,
+    GGML_Q5_0 = 6,
+    GGML_Q5_1 = 7,
     GGML_Q8_0 = 8,
+    GGML_Q2_K = 10,
+    GGML_Q3_K = 11,
     GGML_Q4_K = 12,
+    GGML_Q5_K = 13,
     GGML_Q6_K = 14,
+    GGML_IQ4_NL = 20,
     GGML_BF16 = 30,
 };
 
@@ -47,8 +55,14 @@ struct GgufFile {
     std::vector<uint8_t> read(const GgufTensor& t) const;
 };
 
+// values / bytes of one block of a block-quantized type; 0 for every other type
+int ggml_block_values(int type);
+int ggml_block_bytes(int type);
 // bytes of one row of `ne0` values (block formats: ne0 % block == 0); 0 for unsupported types
 uint64_t ggml_row_bytes(int type, int64_t ne0);
-const char* ggml_type_name(int type);
+// ggml's name of a type in the table above, "type <id>" for any other
+std::string ggml_type_name(int type);
+struct GgufTensor;
+std::string gguf_unsupported(const GgufTensor& t);  // the refusal message of a tensor with nbytes == 0
 
 }  // namespace acemi

@@ -17,10 +17,24 @@
 namespace acemi {
 
 
-// A 2-D weight as read from the file: raw 16-bit values, f32 (F32 files / quantization input), or
-// ggml block rows (GGUF Q8_0 / Q4_K / Q6_K tensors, `qblocks` [rows][row_bytes]).
+// Block rows of one ggml type inside a raw-block matrix ("R"): source row r lands at matrix row
+// row0 + (r / group) * group * step + r % group (BlockSeg, kernels.h).
+struct RawPart {
+    int type = 0;  // ggml type id
+    int64_t rows = 0;
+    int row0 = 0, step = 1, group = 1;
+    std::vector<uint8_t> bytes;
+    std::string name;  // the file's tensor
+};
+
+// A 2-D weight as read from the file: raw 16-bit values, f32 (F32 files / quantization input),
+// ggml block rows of a type with a plane layout (GGUF Q8_0 / Q4_K / Q6_K tensors, `qblocks` [rows][row_bytes]), or
+// row segments of any block types kept as the file's bytes ("R": a tensor of another block type, or a fused matrix
+// whose parts differ in type).
 struct Mat {
-    std::string dtype;  // BF16 | F16 | F32 | Q (blocks)
+    std::string dtype;  // BF16 | F16 | F32 | Q (blocks, one plane type) | R (raw block row segments)
+    std::string name;
+    std::vector<RawPart> parts;  // R
     int64_t rows = 0, cols = 0;
     std::vector<uint16_t> u16;
     std::vector<float> f32;
@@ -38,9 +52,7 @@ struct Mat {
     }
 };
 
-inline quant::QType qtype_of_ggml(int t) {
-    return t == GGML_Q8_0 ? quant::Q8_0 : (t == GGML_Q4_K ? quant::Q4_K : (t == GGML_Q6_K ? quant::Q6_K : quant::QNONE));
-}
+inline int64_t raw_part_row(const RawPart& p, int64_t r) { return p.row0 + (r / p.group) * p.group * p.step + r % p.group; }
 
 inline uint16_t f32_to_bf16_host(float f) {
     uint32_t u;
@@ -63,6 +75,11 @@ struct Loader {
     bool gguf = false;
     std::string wdtype;  // dtype of the 16-bit 2-D weights (BF16 or F16)
     quant::QType qt = quant::QNONE;
+    // raw-block matrices (WF_GGML_RAW) are expanded to their bf16 image once, here, and only the image stays: the
+    // condition / text encoders, whose block runner multiplies resident weights and has no staging scope
+    bool raw_to_image = false;
+    std::string first_raw_name;  // first tensor kept as raw blocks, and its ggml type (the q8 mode's refusal)
+    int first_raw_type = -1;
     Loader(std::vector<void*>& a, size_t& wb) : allocs(a), weight_bytes(wb) {}
 
     template <typename T>
@@ -93,6 +110,8 @@ struct Loader {
                     std::memcpy(&v[(size_t)i], &u, 4);
                 }
             }
+        } else if (const quant::QType q = quant::from_ggml(t.type); q != quant::QNONE && t.ne_at(0) > 0) {
+            quant::dequantize_rows(q, raw.data(), n / t.ne_at(0), t.ne_at(0), v.data());  // any block type, on the host
         } else {
             throw Unsupported("unsupported gguf tensor type for conversion: " + t.name);
         }
@@ -121,11 +140,23 @@ struct Loader {
             const auto& t = gg.get(name);
             if (t.ne_at(2) != 1 || t.ne_at(3) != 1) throw IoError("invalid 2d tensor shape in gguf: " + name);
             if (t.ne_at(0) != cols || t.ne_at(1) != rows) throw IoError("invalid tensor shape for " + name);
-            const quant::QType q = qtype_of_ggml(t.type);
-            if (q != quant::QNONE) {
+            out.name = name;
+            if (!t.nbytes) throw Unsupported(gguf_unsupported(t));
+            const quant::QType q = quant::from_ggml(t.type);
+            if (quant::has_planes(q)) {
                 out.dtype = "Q";
                 out.qt = q;
                 out.qblocks = gg.read(t);
+                return out;
+            }
+            if (q != quant::QNONE) {  // a block type without planes: the file's bytes, expanded on the device
+                out.dtype = "R";
+                RawPart part;
+                part.type = t.type;
+                part.rows = rows;
+                part.bytes = gg.read(t);
+                part.name = name;
+                out.parts.push_back(std::move(part));
                 return out;
             }
             if (t.type == GGML_F16 || t.type == GGML_BF16) {
@@ -140,7 +171,7 @@ struct Loader {
                 out.f32 = gguf_f32(t);
                 return out;
             }
-            throw Unsupported(std::string("unsupported gguf tensor type ") + ggml_type_name(t.type) + ": " + name);
+            throw Unsupported(gguf_unsupported(t));
         }
         const auto& t = st.get(name);
         int64_t r = 1, c = 1;
@@ -202,6 +233,7 @@ struct Loader {
         o.qt = a.qt;
         o.rows = rows;
         o.cols = cols;
+        if (a.dtype == "R") throw Unsupported("raw ggml block rows cannot be permuted: " + a.name);
         if (a.dtype == "Q") {  // whole block rows only (column order is fixed by the blocks)
             const size_t rb = quant::row_bytes(a.qt, a.cols);
             o.qblocks.resize((size_t)rows * rb);
@@ -224,14 +256,47 @@ struct Loader {
             }
         return o;
     }
+    // the row segments of a block-quantized matrix ("Q" or "R"), shifted down by `off` rows
+    static void append_raw(Mat& o, const Mat& p, int64_t off) {
+        if (p.dtype == "Q") {
+            RawPart part;
+            part.type = quant::to_ggml(p.qt);
+            part.rows = p.rows;
+            part.row0 = (int)off;
+            part.bytes = p.qblocks;
+            part.name = p.name;
+            o.parts.push_back(std::move(part));
+            return;
+        }
+        for (RawPart part : p.parts) {
+            part.row0 += (int)off;
+            o.parts.push_back(std::move(part));
+        }
+    }
     static Mat concat_rows(const std::vector<const Mat*>& parts) {
         Mat o;
         o.dtype = parts[0]->dtype;
         o.qt = parts[0]->qt;
         o.cols = parts[0]->cols;
+        o.name = parts[0]->name;
+        bool same = o.dtype != "R", blocks = true;
         for (const Mat* p : parts) {
-            if (p->dtype != o.dtype || p->qt != o.qt || p->cols != o.cols)
-                throw Unsupported("fused weights must share one type");
+            same = same && p->dtype == o.dtype && p->qt == o.qt;
+            blocks = blocks && (p->dtype == "Q" || p->dtype == "R");
+            if (p->cols != o.cols) throw Unsupported("fused weights must share one row length");
+        }
+        if (!same) {  // parts of different types: any mixture of block types stays raw blocks, segment by segment
+            if (!blocks)
+                throw Unsupported("fused weights must share one type (only block-quantized parts may differ): " + o.name);
+            o.dtype = "R";
+            o.qt = quant::QNONE;
+            for (const Mat* p : parts) {
+                append_raw(o, *p, o.rows);
+                o.rows += p->rows;
+            }
+            return o;
+        }
+        for (const Mat* p : parts) {
             o.rows += p->rows;
             o.u16.insert(o.u16.end(), p->u16.begin(), p->u16.end());
             o.f32.insert(o.f32.end(), p->f32.begin(), p->f32.end());
@@ -241,6 +306,18 @@ struct Loader {
     }
     std::vector<float> values(const Mat& a) {
         std::vector<float> v(static_cast<size_t>(a.rows * a.cols));
+        if (a.dtype == "R") {
+            std::vector<float> row((size_t)a.cols);
+            for (const RawPart& p : a.parts) {
+                const quant::QType q = quant::from_ggml(p.type);
+                const size_t rb = quant::row_bytes(q, a.cols);
+                for (int64_t r = 0; r < p.rows; ++r) {
+                    quant::dequantize_rows(q, p.bytes.data() + (size_t)r * rb, 1, a.cols, row.data());
+                    std::memcpy(&v[(size_t)(raw_part_row(p, r) * a.cols)], row.data(), (size_t)a.cols * 4);
+                }
+            }
+            return v;
+        }
         if (a.dtype == "Q") {
             quant::dequantize_rows(a.qt, a.qblocks.data(), a.rows, a.cols, v.data());
             return v;
@@ -259,6 +336,69 @@ struct Loader {
         w.q = upload<uint8_t>(qp.data(), qp.size());
         w.s = upload<float>(sp.data(), sp.size() * 4);
         return w;
+    }
+    // Raw block rows: the file's bytes in one allocation (each segment 16-byte aligned, 16 readable bytes after the
+    // last: launch_dequant_blocks), nothing re-laid out.  raw_to_image: expanded once, only the bf16 image is kept.
+    DevWeight from_raw(const Mat& a) {
+        DevWeight w;
+        w.rows = static_cast<int>(a.rows);
+        w.cols = static_cast<int>(a.cols);
+        size_t total = 16;
+        for (const RawPart& p : a.parts) total += (p.bytes.size() + 15) & ~size_t(15);
+        std::vector<uint8_t> host(total, 0);
+        std::vector<size_t> offs;
+        size_t off = 0;
+        for (const RawPart& p : a.parts) {
+            if (quant::from_ggml(p.type) == quant::QNONE || a.cols % ggml_block_values(p.type) != 0 ||
+                p.bytes.size() != (size_t)p.rows * ggml_row_bytes(p.type, a.cols))
+                throw Unsupported("bad raw block rows: " + p.name);
+            std::memcpy(&host[off], p.bytes.data(), p.bytes.size());
+            offs.push_back(off);
+            off += (p.bytes.size() + 15) & ~size_t(15);
+        }
+        uint8_t* base = upload<uint8_t>(host.data(), host.size());
+        for (size_t i = 0; i < a.parts.size(); ++i) {
+            const RawPart& p = a.parts[i];
+            BlockSeg g;
+            g.type = p.type;
+            g.src = base + offs[i];
+            g.rows = (int)p.rows;
+            g.row0 = p.row0;
+            g.step = p.step;
+            g.group = p.group;
+            w.segs.push_back(g);
+        }
+        w.fmt = WF_GGML_RAW;
+        w.q = base;
+        if (!raw_to_image) {
+            if (first_raw_name.empty() && !a.parts.empty()) {
+                first_raw_name = a.parts[0].name;
+                first_raw_type = a.parts[0].type;
+            }
+            return w;
+        }
+        void* img = nullptr;
+        ACEMI_HIP(hipMalloc(&img, (size_t)a.rows * a.cols * 2));
+        std::vector<DequantBlocksJob> jobs;
+        for (const BlockSeg& g : w.segs) jobs.push_back(DequantBlocksJob{g, w.cols, w.cols, static_cast<uint16_t*>(img)});
+        try {
+            launch_dequant_blocks(jobs.data(), (int)jobs.size(), nullptr);
+            ACEMI_HIP(hipDeviceSynchronize());
+        } catch (...) {
+            (void)hipFree(img);
+            throw;
+        }
+        allocs.pop_back();  // the blocks (the upload above)
+        (void)hipFree(base);
+        weight_bytes -= host.size();
+        allocs.push_back(img);
+        weight_bytes += (size_t)a.rows * a.cols * 2;
+        DevWeight d;
+        d.rows = w.rows;
+        d.cols = w.cols;
+        d.fmt = WF_BF16;
+        d.q = img;
+        return d;
     }
     // F32 weight kept at f32 precision (ggml: F32 mul_mat, activation not rounded): stored as the fp16
     // pair [hi | lo | hi] along K, multiplied with an activation written as [hi | hi | lo]
@@ -285,6 +425,7 @@ struct Loader {
     }
     // try_quantize_matrix (acestep_dit_model.cpp:156-192): quantize when requested and in-dim % block == 0
     DevWeight finish(const Mat& a, bool allow_f32 = false) {
+        if (a.dtype == "R") return from_raw(a);
         if (a.dtype == "Q") return from_blocks(a.qt, a.qblocks.data(), a.rows, a.cols);
         if (quant::applies(qt, a.cols)) {
             const auto v = values(a);
@@ -307,9 +448,9 @@ struct Loader {
     }
     // dense 16-bit copy for the GEMV path: the file bits, or bf16(dequant(q)) for quantized weights
     uint16_t* finish16(const Mat& a, ActType& act) {
-        if (a.dtype == "Q" || quant::applies(qt, a.cols) || a.dtype == "F32") {
+        if (a.dtype == "Q" || a.dtype == "R" || quant::applies(qt, a.cols) || a.dtype == "F32") {
             auto v = values(a);
-            if (a.dtype != "Q" && quant::applies(qt, a.cols)) {
+            if (a.dtype != "Q" && a.dtype != "R" && quant::applies(qt, a.cols)) {
                 std::vector<uint8_t> blocks(static_cast<size_t>(a.rows) * quant::row_bytes(qt, a.cols));
                 quant::quantize_rows(qt, v.data(), a.rows, a.cols, blocks.data());
                 quant::dequantize_rows(qt, blocks.data(), a.rows, a.cols, v.data());
@@ -328,6 +469,21 @@ struct Loader {
         const Mat wg = mat(p + "mlp.gate_proj.weight", I, H);
         const Mat wu = mat(p + "mlp.up_proj.weight", I, H);
         const Mat gu = concat_rows({&wg, &wu});
+        if (gu.dtype == "R") {  // raw blocks: the interleave is the segments' row map (step 2 over 16-row groups)
+            Mat o;
+            o.dtype = "R";
+            o.name = gu.name;
+            o.rows = 2LL * I;
+            o.cols = H;
+            for (const RawPart& src : gu.parts) {
+                RawPart part = src;
+                part.row0 = src.row0 >= I ? 16 : 0;  // gate | up
+                part.step = 2;
+                part.group = 16;
+                o.parts.push_back(std::move(part));
+            }
+            return finish(o);
+        }
         return finish(permute(
             gu, 2LL * I, H,
             [&](int64_t r) {
@@ -341,7 +497,7 @@ struct Loader {
         if (gguf) {  // load_tensor_3d_as_2d_from_gguf (:554-585): ne = (cols, rows, 1)
             const auto& t = gg.get(name);
             if (t.ne_at(0) != cols || t.ne_at(1) != rows || t.ne_at(2) != 1) throw IoError("invalid 3d-as-2d tensor shape in gguf: " + name);
-            const quant::QType q = qtype_of_ggml(t.type);
+            const quant::QType q = quant::from_ggml(t.type);
             if (q != quant::QNONE) {
                 auto raw = gg.read(t);
                 std::vector<float> v((size_t)(rows * cols));

@@ -26,6 +26,38 @@ bool quant_act_from_env() {
     throw std::runtime_error("ACE_MI_QUANT_ACT must be bf16 or q8");
 }
 
+std::string describe_weights(const DitModel& m) {
+    bool fmts[WF_GGML_RAW + 1] = {};
+    std::vector<int> raw_types;
+    auto see = [&](const DevWeight& w) {
+        if (!w.q) return;
+        fmts[w.fmt] = true;
+        for (const BlockSeg& g : w.segs)
+            if (std::find(raw_types.begin(), raw_types.end(), g.type) == raw_types.end()) raw_types.push_back(g.type);
+    };
+    for (const DevWeight* w : {&m.proj_in_w, &m.proj_out_w, &m.cond_w, &m.w_ckv_all, &m.text_proj, &m.lyric.embed,
+                               &m.timbre.embed})
+        see(*w);
+    for (const std::vector<DevLayer>* ls : {&m.layers, &m.lyric.layers, &m.timbre.layers})
+        for (const DevLayer& ly : *ls)
+            for (const DevWeight* w : {&ly.w_qkv, &ly.w_o, &ly.w_cq, &ly.w_ckv, &ly.w_co, &ly.w_gu, &ly.w_down}) see(*w);
+    const char* names[WF_GGML_RAW + 1] = {"bf16",        "f16",         "q8_0 planes",    "q4_K planes",
+                                          "q6_K planes", "f32 (fp16 x3)", "ggml raw blocks"};
+    std::string out;
+    for (int f = 0; f <= WF_GGML_RAW; ++f) {
+        if (!fmts[f]) continue;
+        if (!out.empty()) out += ", ";
+        out += names[f];
+        if (f == WF_GGML_RAW) {
+            std::sort(raw_types.begin(), raw_types.end());
+            out += " (";
+            for (size_t i = 0; i < raw_types.size(); ++i) out += (i ? ", " : "") + ggml_type_name(raw_types[i]);
+            out += ")";
+        }
+    }
+    return out;
+}
+
 void load_config(const std::string& path, DitConfig& c) {
     // acestep_dit_config.cpp:19-93 (required keys + optional ones)
     std::string text;
@@ -226,10 +258,32 @@ void load_dit_model(const std::string& dir, DitModel& m, int& status_hint) {
         // every layer's cross k|v in one [layers*2kd][H] matrix when they share a type (always, except a
         // GGUF file mixing types across layers): the encoder-side projections become one GEMM with
         // N = layers*2kd instead of `layers` GEMMs of M = L rows that fill a quarter of the GPU
-        bool one_type = true;
-        for (int i = 1; i < c.layers; ++i)
+        // (block-quantized layers of differing types -- a layer's k|v may itself be a raw-block matrix -- fuse too:
+        // concat_rows keeps them as one raw-block matrix, segment by segment)
+        bool one_type = true, all_blocks = c.layers > 0;
+        for (int i = 0; i < c.layers; ++i) {
             one_type = one_type && ckv[i].dtype == ckv[0].dtype && ckv[i].qt == ckv[0].qt;
-        if (one_type && c.layers > 0) {
+            all_blocks = all_blocks && (ckv[i].dtype == "Q" || ckv[i].dtype == "R");
+        }
+        if (c.layers > 0 && (ckv[0].dtype == "R" || !one_type) && all_blocks) {
+            std::vector<const Mat*> parts;
+            for (const Mat& x : ckv) parts.push_back(&x);
+            m.w_ckv_all = L.finish(Loader::concat_rows(parts));
+            for (int i = 0; i < c.layers; ++i) {  // layer i's rows: its segments, renumbered from its first row
+                DevWeight v;
+                v.fmt = WF_GGML_RAW;
+                v.rows = 2 * kd;
+                v.cols = m.w_ckv_all.cols;
+                const int r0 = i * 2 * kd;
+                for (BlockSeg g : m.w_ckv_all.segs)
+                    if (g.row0 >= r0 && g.row0 < r0 + 2 * kd) {
+                        g.row0 -= r0;
+                        v.segs.push_back(g);
+                    }
+                v.q = v.segs.empty() ? nullptr : const_cast<void*>(v.segs[0].src);
+                m.layers[i].w_ckv = v;
+            }
+        } else if (one_type && c.layers > 0) {
             std::vector<const Mat*> parts;
             for (const Mat& x : ckv) parts.push_back(&x);
             m.w_ckv_all = L.finish(Loader::concat_rows(parts));
@@ -255,6 +309,7 @@ void load_dit_model(const std::string& dir, DitModel& m, int& status_hint) {
         ckv.clear();
 
         // ---- condition encoders (optional; acestep_dit_model.cpp:885-996)
+        L.raw_to_image = true;  // their block runner multiplies resident weights (loader.h)
         if (L.has("encoder.text_projector.weight")) {
             const auto sh = L.shape2("encoder.text_projector.weight");
             if (sh.first != H) throw IoError("invalid tensor shape for encoder.text_projector.weight");
@@ -299,6 +354,12 @@ void load_dit_model(const std::string& dir, DitModel& m, int& status_hint) {
         };
         load_encoder("encoder.lyric_encoder.", c.lyric_layers, m.lyric);
         load_encoder("encoder.timbre_encoder.", c.timbre_layers, m.timbre);
+        // the quantized-activation parity mode multiplies the block weights themselves (integer dots against planes):
+        // raw blocks have no such GEMM
+        if (quant_act_from_env() && !L.first_raw_name.empty())
+            throw Unsupported("ACE_MI_QUANT_ACT=q8 needs Q8_0 / Q4_K / Q6_K plane weights; this file holds raw ggml "
+                              "block matrices, first " + L.first_raw_name + " (" + ggml_type_name(L.first_raw_type) +
+                              ")");
         m.act = m.layers.empty() ? m.cond_w.act() : m.layers[0].w_qkv.act();
         for (const DevLayer& ly : m.layers)
             for (const DevWeight* w : {&ly.w_qkv, &ly.w_o, &ly.w_cq, &ly.w_ckv, &ly.w_co, &ly.w_gu, &ly.w_down})

@@ -34,19 +34,24 @@ struct DitConfig {
     int timbre_in_dim() const { return timbre_hidden_dim > 0 ? timbre_hidden_dim : (audio_dim > 0 ? audio_dim : 64); }
 };
 
-// A 2-D linear weight [rows = out][cols = in] in HBM: dense 16-bit (file dtype) or one of the
-// ggml block formats re-laid out as q/s planes (runtime/quant.h) when online quantization is on.
+// A 2-D linear weight [rows = out][cols = in] in HBM: dense 16-bit (file dtype), one of the
+// ggml block formats re-laid out as q/s planes (runtime/quant.h; online quantization, or a GGUF matrix that is purely
+// Q8_0 / Q4_K / Q6_K), or raw ggml block rows as the GGUF file holds them (WF_GGML_RAW: `segs`, q = the blocks'
+// allocation; any other block type, or a fused matrix whose parts differ in type).
 struct DevWeight {
     int fmt = WF_BF16;
     void* q = nullptr;
     float* s = nullptr;
     int rows = 0, cols = 0;
-    WeightView view() const {
+    std::vector<BlockSeg> segs;  // WF_GGML_RAW
+    WeightView view() const {  // (a raw view points into this DevWeight's segs: views of weights that stay loaded)
         WeightView v;
         v.fmt = fmt == WF_F32X3 ? WF_F16 : fmt;
         v.q = q;
         v.s = s;
         v.ld = fmt == WF_F32X3 ? 3 * cols : cols;
+        v.segs = segs.data();
+        v.n_segs = (int)segs.size();
         return v;
     }
     int k_mult() const { return fmt == WF_F32X3 ? 3 : 1; }  // GEMM K = k_mult * cols
@@ -130,6 +135,10 @@ struct DitModel {
 // ACE_MI_QUANT_ACT=q8: the ggml-faithful quantized-activation mode (DitEngine::walk<true>); anything else (the
 // default, "bf16") = the product arithmetic, bf16 activations x bf16(dequant(W))
 bool quant_act_from_env();
+
+// The formats of the loaded 2-D weights in words, e.g. "bf16", "q4_K planes", "ggml raw blocks (q5_K, q6_K)" or a
+// comma-separated mixture (ace_mi_dit_weight_desc).
+std::string describe_weights(const DitModel& m);
 
 // Throws std::runtime_error with a reference-style message on failure.
 // `status_hint` receives 3 (IO) or 4 (UNSUPPORTED) for the ABI status code.

@@ -2,6 +2,8 @@
 // -ffp-contract=off: every float expression rounds where ggml's scalar C does.
 #include "quant.h"
 
+#include "../kernels.h"
+
 #include <algorithm>
 #include <cctype>
 #include <cmath>
@@ -366,6 +368,137 @@ void q6_k_deq(const uint8_t* y, int64_t k, float* x) {
     }
 }
 
+// ---------------------------------------------------------------- decode-only types (ggml dequantize_row_*)
+inline float f16_at(const uint8_t* p) {
+    uint16_t h;
+    std::memcpy(&h, p, 2);
+    return fp16_to_fp32(h);
+}
+inline uint32_t u32_at(const uint8_t* p) {
+    uint32_t v;
+    std::memcpy(&v, p, 4);
+    return v;
+}
+const int8_t kvalues_iq4nl[16] = {-127, -104, -83, -65, -49, -35, -22, -10, 1, 13, 25, 38, 53, 69, 89, 113};
+
+// block_q4_0 {d, qs[16]} / block_q4_1 {d, m, qs[16]} / block_iq4_nl {d, qs[16]}: value j in the low nibble of qs[j],
+// value j + 16 in its high nibble
+void q4_0_deq(const uint8_t* y, int64_t k, float* x) {
+    for (int64_t i = 0; i < k / 32; ++i, y += 18, x += 32) {
+        const float d = f16_at(y);
+        for (int j = 0; j < 16; ++j) {
+            x[j] = (float)((y[2 + j] & 0xF) - 8) * d;
+            x[j + 16] = (float)((y[2 + j] >> 4) - 8) * d;
+        }
+    }
+}
+void q4_1_deq(const uint8_t* y, int64_t k, float* x) {
+    for (int64_t i = 0; i < k / 32; ++i, y += 20, x += 32) {
+        const float d = f16_at(y), m = f16_at(y + 2);
+        for (int j = 0; j < 16; ++j) {
+            x[j] = (float)(y[4 + j] & 0xF) * d + m;
+            x[j + 16] = (float)(y[4 + j] >> 4) * d + m;
+        }
+    }
+}
+void iq4_nl_deq(const uint8_t* y, int64_t k, float* x) {
+    for (int64_t i = 0; i < k / 32; ++i, y += 18, x += 32) {
+        const float d = f16_at(y);
+        for (int j = 0; j < 16; ++j) {
+            x[j] = d * (float)kvalues_iq4nl[y[2 + j] & 0xF];
+            x[j + 16] = d * (float)kvalues_iq4nl[y[2 + j] >> 4];
+        }
+    }
+}
+// block_q5_0 {d, qh[4], qs[16]} / block_q5_1 {d, m, qh[4], qs[16]}: bit v of the little-endian qh word is the fifth
+// bit of value v
+void q5_0_deq(const uint8_t* y, int64_t k, float* x) {
+    for (int64_t i = 0; i < k / 32; ++i, y += 22, x += 32) {
+        const float d = f16_at(y);
+        const uint32_t qh = u32_at(y + 2);
+        for (int j = 0; j < 16; ++j) {
+            const int x0 = (y[6 + j] & 0xF) | (int)(((qh >> j) & 1) << 4);
+            const int x1 = (y[6 + j] >> 4) | (int)(((qh >> (j + 16)) & 1) << 4);
+            x[j] = (float)(x0 - 16) * d;
+            x[j + 16] = (float)(x1 - 16) * d;
+        }
+    }
+}
+void q5_1_deq(const uint8_t* y, int64_t k, float* x) {
+    for (int64_t i = 0; i < k / 32; ++i, y += 24, x += 32) {
+        const float d = f16_at(y), m = f16_at(y + 2);
+        const uint32_t qh = u32_at(y + 4);
+        for (int j = 0; j < 16; ++j) {
+            const int x0 = (y[8 + j] & 0xF) | (int)(((qh >> j) & 1) << 4);
+            const int x1 = (y[8 + j] >> 4) | (int)(((qh >> (j + 16)) & 1) << 4);
+            x[j] = (float)x0 * d + m;
+            x[j + 16] = (float)x1 * d + m;
+        }
+    }
+}
+// block_q2_K {scales[16], qs[64], d, dmin}: 16 values per scale byte (low nibble scale, high nibble min)
+void q2_k_deq(const uint8_t* y, int64_t k, float* x) {
+    for (int64_t i = 0; i < k / QK_K; ++i, y += 84) {
+        const float d = f16_at(y + 80), min = f16_at(y + 82);
+        const uint8_t* q = y + 16;
+        int is = 0;
+        for (int n = 0; n < QK_K; n += 128, q += 32) {
+            for (int shift = 0; shift < 8; shift += 2) {
+                for (int half = 0; half < 2; ++half) {
+                    const uint8_t sc = y[is++];
+                    const float dl = d * (float)(sc & 0xF), ml = min * (float)(sc >> 4);
+                    for (int l = 0; l < 16; ++l) *x++ = dl * (float)((q[l + 16 * half] >> shift) & 3) - ml;
+                }
+            }
+        }
+    }
+}
+// block_q3_K {hmask[32], qs[64], scales[12], d}: sixteen 6-bit scales (low nibbles in bytes 0..7, two high bits each in
+// bytes 8..11); bit (4n + j) of hmask[l] CLEAR subtracts 4 from value 128n + 32j + l
+void q3_k_deq(const uint8_t* y, int64_t k, float* x) {
+    for (int64_t i = 0; i < k / QK_K; ++i, y += 110) {
+        const float d_all = f16_at(y + 108);
+        const uint8_t* s = y + 96;
+        int8_t scales[16];
+        for (int kk = 0; kk < 16; ++kk) {
+            const int lo = kk < 8 ? (s[kk] & 0xF) : (s[kk - 8] >> 4);
+            const int hi = (s[8 + (kk & 3)] >> (2 * (kk >> 2))) & 3;
+            scales[kk] = (int8_t)((lo | (hi << 4)) - 32);
+        }
+        const uint8_t* q = y + 32;
+        const uint8_t* hm = y;
+        int is = 0;
+        uint8_t m = 1;
+        for (int n = 0; n < QK_K; n += 128, q += 32) {
+            for (int shift = 0; shift < 8; shift += 2, m <<= 1) {
+                for (int half = 0; half < 2; ++half) {
+                    const float dl = d_all * (float)scales[is++];
+                    for (int l = 16 * half; l < 16 * half + 16; ++l)
+                        *x++ = dl * (float)((int)((q[l] >> shift) & 3) - ((hm[l] & m) ? 0 : 4));
+                }
+            }
+        }
+    }
+}
+// block_q5_K {d, dmin, scales[12], qh[32], qs[128]}: block_q4_K with a fifth bit, bit `is` of qh[l] for sub-block `is`
+void q5_k_deq(const uint8_t* y, int64_t k, float* x) {
+    for (int64_t i = 0; i < k / QK_K; ++i, y += 176) {
+        const float d = f16_at(y), min = f16_at(y + 2);
+        const uint8_t* qh = y + 16;
+        const uint8_t* ql = y + 48;
+        int is = 0;
+        for (int j = 0; j < QK_K; j += 64, ql += 32, is += 2) {
+            uint8_t sc, m;
+            get_scale_min_k4(is + 0, y + 4, &sc, &m);
+            const float d1 = d * sc, m1 = min * m;
+            get_scale_min_k4(is + 1, y + 4, &sc, &m);
+            const float d2 = d * sc, m2 = min * m;
+            for (int l = 0; l < 32; ++l) *x++ = d1 * (float)((ql[l] & 0xF) + (((qh[l] >> is) & 1) << 4)) - m1;
+            for (int l = 0; l < 32; ++l) *x++ = d2 * (float)((ql[l] >> 4) + (((qh[l] >> (is + 1)) & 1) << 4)) - m2;
+        }
+    }
+}
+
 template <typename F>
 void parallel_rows(int64_t rows, F&& f) {
     unsigned nt = std::thread::hardware_concurrency();
@@ -405,21 +538,51 @@ QType from_env(const char* primary_key) {
 
 QType from_env() { return from_env("ACE_GGML_DIT_WEIGHT_QTYPE"); }
 
+namespace {
+struct TypeRow {
+    QType t;
+    int ggml, values, bytes;
+    const char* name;
+};
+constexpr TypeRow kTypes[] = {
+    {Q8_0, 8, 32, 34, "Q8_0"},   {Q4_K, 12, 256, 144, "Q4_K"}, {Q6_K, 14, 256, 210, "Q6_K"}, {Q4_0, 2, 32, 18, "Q4_0"},
+    {Q4_1, 3, 32, 20, "Q4_1"},   {Q5_0, 6, 32, 22, "Q5_0"},    {Q5_1, 7, 32, 24, "Q5_1"},    {Q2_K, 10, 256, 84, "Q2_K"},
+    {Q3_K, 11, 256, 110, "Q3_K"}, {Q5_K, 13, 256, 176, "Q5_K"}, {IQ4_NL, 20, 32, 18, "IQ4_NL"},
+};
+const TypeRow* type_row(QType t) {
+    for (const TypeRow& r : kTypes)
+        if (r.t == t) return &r;
+    return nullptr;
+}
+}  // namespace
+
 const char* name(QType t) {
-    switch (t) {
-        case Q8_0: return "Q8_0";
-        case Q4_K: return "Q4_K";
-        case Q6_K: return "Q6_K";
-        default: return "none";
-    }
+    const TypeRow* r = type_row(t);
+    return r ? r->name : "none";
+}
+QType from_ggml(int ggml_type) {
+    for (const TypeRow& r : kTypes)
+        if (r.ggml == ggml_type) return r.t;
+    return QNONE;
+}
+int to_ggml(QType t) {
+    const TypeRow* r = type_row(t);
+    return r ? r->ggml : -1;
 }
 
-int block_values(QType t) { return t == Q8_0 ? QK8_0 : QK_K; }
-size_t block_bytes(QType t) { return t == Q8_0 ? 34 : (t == Q4_K ? 144 : 210); }
+int block_values(QType t) {
+    const TypeRow* r = type_row(t);
+    return r ? r->values : QK_K;
+}
+size_t block_bytes(QType t) {
+    const TypeRow* r = type_row(t);
+    return r ? (size_t)r->bytes : 0;
+}
 size_t row_bytes(QType t, int64_t cols) { return (size_t)(cols / block_values(t)) * block_bytes(t); }
-bool applies(QType t, int64_t cols) { return t != QNONE && cols % block_values(t) == 0; }
+bool applies(QType t, int64_t cols) { return type_row(t) != nullptr && cols % block_values(t) == 0; }
 
 void quantize_rows(QType t, const float* src, int64_t rows, int64_t cols, uint8_t* dst) {
+    if (!has_planes(t)) throw std::runtime_error("quantize: no encoder for this type");
     if (!applies(t, cols)) throw std::runtime_error("quantize: bad row length");
     const size_t rb = row_bytes(t, cols);
     parallel_rows(rows, [&](int64_t r0, int64_t r1) {
@@ -442,12 +605,20 @@ void dequantize_rows(QType t, const uint8_t* src, int64_t rows, int64_t cols, fl
     for (int64_t r = 0; r < rows; ++r) {
         const uint8_t* y = src + r * rb;
         float* x = dst + r * cols;
-        if (t == Q8_0)
-            q8_0_deq(y, cols, x);
-        else if (t == Q4_K)
-            q4_k_deq(y, cols, x);
-        else
-            q6_k_deq(y, cols, x);
+        switch (t) {
+            case Q8_0: q8_0_deq(y, cols, x); break;
+            case Q4_K: q4_k_deq(y, cols, x); break;
+            case Q6_K: q6_k_deq(y, cols, x); break;
+            case Q4_0: q4_0_deq(y, cols, x); break;
+            case Q4_1: q4_1_deq(y, cols, x); break;
+            case Q5_0: q5_0_deq(y, cols, x); break;
+            case Q5_1: q5_1_deq(y, cols, x); break;
+            case Q2_K: q2_k_deq(y, cols, x); break;
+            case Q3_K: q3_k_deq(y, cols, x); break;
+            case Q5_K: q5_k_deq(y, cols, x); break;
+            case IQ4_NL: iq4_nl_deq(y, cols, x); break;
+            default: throw std::runtime_error("dequantize: bad type");
+        }
     }
 }
 
@@ -522,4 +693,32 @@ void to_planes(QType t, const uint8_t* blocks, int64_t rows, int64_t cols, uint8
 }
 
 }  // namespace quant
+
+#ifndef __HIP__
+// Host build of the runtime (no device compiler: the CPU tests' libraries, whose other launch_* are host loops too).
+// launch_dequant_blocks on the host: each segment's rows through quant::dequantize_rows (ggml's CPU arithmetic, the
+// kernel's contract), RNE to bf16, at the segment's row map.
+void launch_dequant_blocks(const DequantBlocksJob* jobs, int n, hipStream_t) {
+    for (int ji = 0; ji < n; ++ji) {
+        const DequantBlocksJob& j = jobs[ji];
+        const quant::QType q = quant::from_ggml(j.seg.type);
+        ACEMI_CHECK(q != quant::QNONE && j.seg.src && j.out && j.seg.rows > 0 && quant::applies(q, j.K) &&
+                        j.ld >= j.K && j.seg.step >= 1 && j.seg.group >= 1,
+                    "dequant_blocks: bad job");
+        const size_t rb = quant::row_bytes(q, j.K);
+        std::vector<float> row((size_t)j.K);
+        for (int r = 0; r < j.seg.rows; ++r) {
+            quant::dequantize_rows(q, static_cast<const uint8_t*>(j.seg.src) + (size_t)r * rb, 1, j.K, row.data());
+            uint16_t* dst = j.out + (int64_t)block_seg_row(j.seg, r) * j.ld;
+            for (int i = 0; i < j.K; ++i) {
+                uint32_t u;
+                std::memcpy(&u, &row[(size_t)i], 4);
+                u += 0x7fffu + ((u >> 16) & 1u);
+                dst[i] = (uint16_t)(u >> 16);
+            }
+        }
+    }
+}
+#endif
+
 }  // namespace acemi

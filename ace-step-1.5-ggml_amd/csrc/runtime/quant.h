@@ -21,7 +21,16 @@
 namespace acemi {
 namespace quant {
 
-enum QType : int { QNONE = 0, Q8_0 = 1, Q4_K = 2, Q6_K = 3 };
+// Q8_0 / Q4_K / Q6_K: encoders, decoders and the plane layout.  The types after them are decode-only: GGUF files carry
+// them, dequantize_rows reads them, and on the device they stay raw ggml blocks (WF_GGML_RAW, kernels.h).
+enum QType : int {
+    QNONE = 0, Q8_0 = 1, Q4_K = 2, Q6_K = 3,
+    Q4_0 = 4, Q4_1 = 5, Q5_0 = 6, Q5_1 = 7, Q2_K = 8, Q3_K = 9, Q5_K = 10, IQ4_NL = 11,
+};
+inline bool has_planes(QType t) { return t == Q8_0 || t == Q4_K || t == Q6_K; }
+// ggml type id (runtime/gguf.h) <-> QType; QNONE / -1 for a type that is not block-quantized
+QType from_ggml(int ggml_type);
+int to_ggml(QType t);
 
 // parse_quant_type (acestep_dit_model.cpp:27-37): Q8/Q8_0, Q6/Q6_K, Q4/Q4_K/Q4_K_M (case-insensitive)
 QType parse(const char* s);
@@ -31,14 +40,15 @@ QType from_env();
 QType from_env(const char* primary_key);
 const char* name(QType t);
 
-int block_values(QType t);       // 32 / 256 / 256
-size_t block_bytes(QType t);     // 34 / 144 / 210
+int block_values(QType t);       // 32 / 256 (K-quants)
+size_t block_bytes(QType t);     // 34 / 144 / 210; the decode-only types as in ggml_block_bytes
 size_t row_bytes(QType t, int64_t cols);
 bool applies(QType t, int64_t cols);  // in-dim % block == 0
 
 // ggml block bytes of `rows` rows of `cols` f32 values (multithreaded over rows).
 void quantize_rows(QType t, const float* src, int64_t rows, int64_t cols, uint8_t* dst);
-// ggml dequantize_row_* to f32.
+// ggml's CPU dequantize_row_* to f32, every QType.  Each value is one f32 expression whose products are exact (an fp16
+// scale times a small integer), so it rounds at most once and reads the same with or without FMA contraction.
 void dequantize_rows(QType t, const uint8_t* src, int64_t rows, int64_t cols, float* dst);
 
 // Plane sizes (bytes) and conversion for the device layout described above.

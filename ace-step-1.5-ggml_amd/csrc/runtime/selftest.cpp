@@ -338,6 +338,142 @@ ace_ggml_status ace_mi_kernel_dequant(int32_t qtype, int32_t N, int32_t K, const
     return ACE_GGML_OK;
 }
 
+// Raw-block expansion (kernels/dequant_blocks.hip) of n_segs row segments into one host matrix out [total_rows][K]
+// of bf16 words, whose initial content is kept wherever no segment writes.  Blocks are host pointers.
+ace_ggml_status ace_mi_kernel_dequant_segments(int32_t n_segs, const ace_mi_block_seg* segs, int32_t total_rows,
+                                               int32_t K, uint16_t* out) {
+    using namespace acemi;
+    if (!segs || !out || n_segs <= 0 || total_rows <= 0 || K <= 0) return ACE_GGML_ERR_INVALID_ARG;
+    for (int i = 0; i < n_segs; ++i) {  // every row a segment may write lies inside the host matrix
+        const ace_mi_block_seg& g = segs[i];
+        const quant::QType q = quant::from_ggml(g.type);
+        if (q == quant::QNONE || !g.blocks || g.rows <= 0 || g.row0 < 0 || g.step < 1 || g.group < 1 ||
+            !quant::applies(q, K))
+            return ACE_GGML_ERR_INVALID_ARG;
+        BlockSeg b;
+        b.row0 = g.row0;
+        b.step = g.step;
+        b.group = g.group;
+        for (int r = 0; r < g.rows; ++r)
+            if (block_seg_row(b, r) >= total_rows) return ACE_GGML_ERR_INVALID_ARG;
+    }
+    try {
+        std::vector<std::unique_ptr<DevMem>> src;
+        DevMem dout((size_t)total_rows * K * 2);
+        ACEMI_HIP(hipMemcpy(dout.p, out, (size_t)total_rows * K * 2, hipMemcpyHostToDevice));
+        std::vector<DequantBlocksJob> jobs;
+        for (int i = 0; i < n_segs; ++i) {
+            const ace_mi_block_seg& g = segs[i];
+            const size_t bytes = (size_t)g.rows * quant::row_bytes(quant::from_ggml(g.type), K);
+            src.emplace_back(new DevMem(((bytes + 15) & ~size_t(15)) + 16));
+            ACEMI_HIP(hipMemcpy(src.back()->p, g.blocks, bytes, hipMemcpyHostToDevice));
+            DequantBlocksJob j;
+            j.seg.type = g.type;
+            j.seg.src = src.back()->p;
+            j.seg.rows = g.rows;
+            j.seg.row0 = g.row0;
+            j.seg.step = g.step;
+            j.seg.group = g.group;
+            j.K = K;
+            j.ld = K;
+            j.out = dout.as<uint16_t>();
+            jobs.push_back(j);
+        }
+        launch_dequant_blocks(jobs.data(), (int)jobs.size(), nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        ACEMI_HIP(hipMemcpy(out, dout.p, (size_t)total_rows * K * 2, hipMemcpyDeviceToHost));
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_dequant_segments: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+// One matrix of one ggml type: out = bf16 words [N][K].
+ace_ggml_status ace_mi_kernel_dequant_blocks(int32_t type, int32_t N, int32_t K, const uint8_t* blocks, uint16_t* out) {
+    ace_mi_block_seg g{};
+    g.type = type;
+    g.rows = N;
+    g.row0 = 0;
+    g.step = 1;
+    g.group = 1;
+    g.blocks = blocks;
+    return ace_mi_kernel_dequant_segments(1, &g, N, K, out);
+}
+
+// Time of one expansion of an [N][K] matrix, averaged over iters launches that rotate through enough copies of the
+// blocks and of the image to exceed the memory-side cache: planes = 0 the raw-block kernel on ggml type `type`,
+// planes = 1 the plane kernel (launch_dequant_bf16; Q8_0 / Q4_K / Q6_K).  The blocks are valid but arbitrary.
+ace_ggml_status ace_mi_bench_dequant_blocks(int32_t type, int32_t planes, int32_t N, int32_t K, int32_t iters,
+                                            float* avg_ms) {
+    using namespace acemi;
+    const quant::QType q = quant::from_ggml(type);
+    if (!avg_ms || q == quant::QNONE || N <= 0 || iters <= 0 || !quant::applies(q, K) ||
+        (planes && !quant::has_planes(q)))
+        return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const size_t rb = quant::row_bytes(q, K), bytes = (size_t)N * rb;
+        std::vector<uint8_t> blocks(bytes);
+        for (size_t i = 0; i < bytes; ++i) blocks[i] = (uint8_t)(0x21u + (i * 37u) % 0x17u);  // fp16 fields: small, finite
+        const size_t in_b = ((bytes + 15) & ~size_t(15)) + 16, out_b = (size_t)N * K * 2;
+        const size_t qp_b = planes ? quant::q_plane_bytes(q, N, K) : 0, sp_b = planes ? quant::s_plane_floats(q, N, K) * 4 : 0;
+        const size_t per = (planes ? qp_b + sp_b : in_b) + out_b;
+        const int R = (int)std::max<size_t>(2, std::min<size_t>(32, ((size_t)640 << 20) / per + 1));
+        std::vector<std::unique_ptr<DevMem>> in, in2, img;
+        std::vector<uint8_t> qp(qp_b);
+        std::vector<float> sp(sp_b / 4);
+        if (planes) quant::to_planes(q, blocks.data(), N, K, qp.data(), sp.data());
+        for (int r = 0; r < R; ++r) {
+            img.emplace_back(new DevMem(out_b));
+            if (planes) {
+                in.emplace_back(new DevMem(qp_b));
+                in2.emplace_back(new DevMem(sp_b));
+                ACEMI_HIP(hipMemcpy(in.back()->p, qp.data(), qp_b, hipMemcpyHostToDevice));
+                ACEMI_HIP(hipMemcpy(in2.back()->p, sp.data(), sp_b, hipMemcpyHostToDevice));
+            } else {
+                in.emplace_back(new DevMem(in_b));
+                ACEMI_HIP(hipMemcpy(in.back()->p, blocks.data(), bytes, hipMemcpyHostToDevice));
+            }
+        }
+        auto run = [&](int i) {
+            const int r = i % R;
+            if (planes) {
+                WeightView w;
+                w.fmt = q == quant::Q8_0 ? WF_Q8_0 : q == quant::Q4_K ? WF_Q4_K : WF_Q6_K;
+                w.q = in[r]->p;
+                w.s = in2[r]->as<float>();
+                launch_dequant_bf16(w, N, K, img[r]->as<uint16_t>(), nullptr);
+            } else {
+                DequantBlocksJob j;
+                j.seg.type = type;
+                j.seg.src = in[r]->p;
+                j.seg.rows = N;
+                j.K = K;
+                j.ld = K;
+                j.out = img[r]->as<uint16_t>();
+                launch_dequant_blocks(&j, 1, nullptr);
+            }
+        };
+        hipEvent_t e0, e1;
+        ACEMI_HIP(hipEventCreate(&e0));
+        ACEMI_HIP(hipEventCreate(&e1));
+        for (int i = 0; i < 3; ++i) run(i);
+        ACEMI_HIP(hipEventRecord(e0, nullptr));
+        for (int i = 0; i < iters; ++i) run(i + 3);
+        ACEMI_HIP(hipEventRecord(e1, nullptr));
+        ACEMI_HIP(hipEventSynchronize(e1));
+        float ms = 0.f;
+        ACEMI_HIP(hipEventElapsedTime(&ms, e0, e1));
+        *avg_ms = ms / iters;
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_bench_dequant_blocks: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
 // LoRA merge kernel: n_jobs jobs of one launch on one host matrix pair (include/acestep_mi355x_selftest.h).
 ace_ggml_status ace_mi_kernel_lora_merge(int32_t fmt, int32_t total_rows, int32_t cols, int32_t ld_base, int32_t ld_out,
                                          const uint16_t* base, uint16_t* out, const ace_mi_lora_job* jobs,

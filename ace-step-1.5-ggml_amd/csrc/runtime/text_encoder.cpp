@@ -83,6 +83,7 @@ void load_text_model(const std::string& dir, TextModel& m) {
     // get_quant_type_from_env (qwen_model.cpp:38-44); the GGUF loaders keep the file's types
     L.qt = gguf_path.empty() ? quant::from_env("ACE_GGML_QWEN_WEIGHT_QTYPE") : quant::QNONE;
     m.qtype = L.qt;
+    L.raw_to_image = true;  // GGUF block types without a plane layout: expanded once to bf16 (loader.h)
     if (!gguf_path.empty()) {
         L.gguf = true;
         L.gg.open(gguf_path);

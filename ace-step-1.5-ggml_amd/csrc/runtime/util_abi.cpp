@@ -34,9 +34,7 @@ int64_t ace_mi_quantize(int32_t qtype, const float* src, int64_t rows, int64_t c
 ace_ggml_status ace_mi_dequantize(int32_t qtype, const uint8_t* src, int64_t rows, int64_t cols, float* dst) {
     using namespace acemi;
     const auto t = static_cast<quant::QType>(qtype);
-    if (!src || !dst || rows <= 0 || (t != quant::Q8_0 && t != quant::Q4_K && t != quant::Q6_K) ||
-        !quant::applies(t, cols))
-        return ACE_GGML_ERR_INVALID_ARG;
+    if (!src || !dst || rows <= 0 || !quant::applies(t, cols)) return ACE_GGML_ERR_INVALID_ARG;  // (any QType)
     quant::dequantize_rows(t, src, rows, cols, dst);
     return ACE_GGML_OK;
 }

@@ -42,6 +42,12 @@ ACE_GGML_API ace_ggml_status ace_mi_create_on_device(const ace_ggml_init_params*
 /* Model dimensions of the loaded DiT (ACE_GGML_ERR "dit not loaded" otherwise). */
 ACE_GGML_API ace_ggml_status ace_mi_dit_get_info(ace_ggml_context* ctx, ace_mi_dit_info* out);
 
+/* The device formats of the loaded DiT's 2-D weights as a NUL-terminated string (truncated to buf_size): "bf16", "f16",
+ * "q8_0 planes" / "q4_K planes" / "q6_K planes" (online quantization, or a GGUF matrix purely of that type),
+ * "f32 (fp16 x3)", "ggml raw blocks (<types>)" (GGUF matrices of any other block type, or fused from parts of
+ * different block types: the file's bytes, expanded to bf16 by the staged-dequant scopes), comma-separated when mixed. */
+ACE_GGML_API ace_ggml_status ace_mi_dit_weight_desc(ace_ggml_context* ctx, char* buf, size_t buf_size);
+
 /* One denoising step for `batch` samples sharing (seq_len, enc_len).
  * d_hidden [B][T][audio], d_context [B][T][in-audio] (either may be NULL = zeros),
  * d_enc [B][L][hidden] (NULL only if enc_len == 0), d_mask [B][T] / d_enc_mask [B][L] int32
@@ -156,7 +162,8 @@ ACE_GGML_API ace_ggml_status ace_mi_vae_encode_device(ace_ggml_context* ctx, con
  * ggml block bytes.  Returns the byte count written, or -1 (bad type / cols % block / dst too small). */
 ACE_GGML_API int64_t ace_mi_quantize(int32_t qtype, const float* src, int64_t rows, int64_t cols, uint8_t* dst,
                                      size_t dst_size);
-/* ggml dequantize_row_* of block rows to f32. */
+/* ggml dequantize_row_* of block rows to f32: the three types above and the decode-only ones, 4 = Q4_0, 5 = Q4_1,
+ * 6 = Q5_0, 7 = Q5_1, 8 = Q2_K, 9 = Q3_K, 10 = Q5_K, 11 = IQ4_NL (ace_mi_quantize keeps its three). */
 ACE_GGML_API ace_ggml_status ace_mi_dequantize(int32_t qtype, const uint8_t* src, int64_t rows, int64_t cols,
                                                float* dst);
 /* ---- condition encoders: the conditioning half of

@@ -51,6 +51,24 @@ ACE_GGML_API ace_ggml_status ace_mi_kernel_gemm_q(int32_t qtype, int32_t epi, in
  * bf16(dequant(W)) [N][K] for ggml block rows W [N][K]. */
 ACE_GGML_API ace_ggml_status ace_mi_kernel_dequant(int32_t qtype, int32_t N, int32_t K, const uint8_t* W_blocks,
                                                    uint16_t* out);
+/* Raw ggml block rows -> bf16 image (the expansion of a raw-block weight, csrc/kernels/dequant_blocks.hip): ggml type ids
+ * 2 Q4_0, 3 Q4_1, 6 Q5_0, 7 Q5_1, 8 Q8_0, 10 Q2_K, 11 Q3_K, 12 Q4_K, 13 Q5_K, 14 Q6_K, 20 IQ4_NL.  out = bf16 bits
+ * of rne_bf16(ggml dequantize_row_*(blocks)) [N][K]. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_dequant_blocks(int32_t type, int32_t N, int32_t K, const uint8_t* blocks,
+                                                          uint16_t* out);
+/* The segment form: source row r of segment i lands at row  row0 + (r / group) * group * step + r % group  of the host
+ * matrix out [total_rows][K] (bf16 words), which keeps its content wherever no segment writes; all segments in one call
+ * of the launch entry (one launch per type). */
+typedef struct ace_mi_block_seg {
+    int32_t type, rows, row0, step, group;
+    const uint8_t* blocks; /* [rows][K / block][block bytes] */
+} ace_mi_block_seg;
+ACE_GGML_API ace_ggml_status ace_mi_kernel_dequant_segments(int32_t n_segs, const ace_mi_block_seg* segs,
+                                                            int32_t total_rows, int32_t K, uint16_t* out);
+/* Average time (ms) of one [N][K] expansion over iters launches on rotating buffers: planes 0 = the raw-block kernel,
+ * 1 = the plane kernel of ace_mi_kernel_dequant on the same blocks (types 8, 12, 14). */
+ACE_GGML_API ace_ggml_status ace_mi_bench_dequant_blocks(int32_t type, int32_t planes, int32_t N, int32_t K,
+                                                         int32_t iters, float* avg_ms);
 /* ggml-faithful quantized-activation GEMM (ACE_MI_QUANT_ACT=q8): x f32 [M][K] quantized on the device to Q8_0
  * (Q8_0 weights) or Q8_K (K-quants) blocks -- returned as q_out int8 [M][K], s_out f32 [K/32][M] (block scale d),
  * bsum_out f32 [K/32][M] (sum of q per 32, Q8_K) when non-null -- then ggml's per-block integer dot products against
