@@ -6,7 +6,6 @@
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
-#include <cstdio>
 #include <cstring>
 #include <map>
 #include <tuple>
@@ -26,171 +25,47 @@ DitEngine::DitEngine(int device) : device_(device) {
     set_attn_precision(prec);
     const char* u = std::getenv("ACE_MI_UNFUSED_PREP");
     fused_prep_ = !(u && u[0] && u[0] != '0');
-    const char* q = std::getenv("ACE_MI_QUANT_STAGED");
-    staged_quant_ = !(q && q[0] == '0');
-    const char* h = std::getenv("ACE_MI_QUANT_STAGE_SCOPE");
-    stage_per_call_ = !(h && std::strcmp(h, "layer") == 0);
-    stage_model_ = !(h && (std::strcmp(h, "call") == 0 || std::strcmp(h, "layer") == 0));  // default: model
     if (const char* pf = std::getenv("ACE_MI_WEIGHT_PREFETCH")) prefetch_blocks_ = std::max(0, std::atoi(pf));
     qact_ = quant_act_from_env();
     // TEST ONLY (self-test library builds): ACE_MI_TEST_FAULT, runtime/test_hooks.cpp
     if (!test_fault_from_env(fault_.layer, fault_.row, fault_.col, fault_.amp)) fault_.layer = -1;
 }
 
-DitEngine::~DitEngine() {
-    for (Buf* b : {&a0_, &x_, &act_, &attn_, &act2_, &qkv_, &qh_, &kh_, &vt_, &kbias_, &enc_act_, &encp_, &ckv_, &kc_,
-                   &vc_, &kbias_c_, &attn_part_, &freq_, &freq_act_, &th_, &th_act_, &temb_t_, &temb_r_, &temb_act_, &proj_,
-                   &mods_, &outmod_, &cos_, &sin_, &ein_, &knorm_tab_, &ts_proj_, &ts_temb_t_, &ts_temb_r_, &qf_, &qa_,
-                   &qs_, &qb_, &encf_}) {
-        if (b->p) (void)hipFree(b->p);
-    }
+DitEngine::~DitEngine() {  // (every Buf, and images_, frees itself)
     if (pf_stream_) {
         (void)hipStreamSynchronize(pf_stream_);
         (void)hipStreamDestroy(pf_stream_);
     }
     if (pf_ev_) (void)hipEventDestroy(pf_ev_);
     if (pf_done_) (void)hipEventDestroy(pf_done_);
-    if (pf_sink_.p) (void)hipFree(pf_sink_.p);
-    if (stage_ev_) (void)hipEventDestroy(stage_ev_);
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
-    if (wring_.p) (void)hipFree(wring_.p);
-    for (auto& kv : img_)
-        if (kv.second.p) (void)hipFree(kv.second.p);
-    for (auto& kv : q8img_)
-        if (kv.second.p) (void)hipFree(kv.second.p);
-    if (qa16_.p) (void)hipFree(qa16_.p);
     free_lora();
 }
 
-namespace {
-size_t wbytes(const DevWeight& w) { return (size_t)w.rows * w.cols * 2; }
-
-// The bf16 images of quantized matrices: plane formats through launch_dequant_bf16_batch (one launch per format),
-// raw-block matrices through launch_dequant_blocks (one job per row segment, one launch per ggml type).
-struct Expander {
-    DequantJob planes[8];
-    int n_planes = 0;
-    std::vector<DequantBlocksJob> blocks;
-    void add(const WeightView& v, int rows, int cols, uint16_t* out, hipStream_t s) {
-        if (v.fmt == WF_GGML_RAW) {
-            for (int i = 0; i < v.n_segs; ++i) blocks.push_back(DequantBlocksJob{v.segs[i], cols, cols, out});
-            return;
-        }
-        if (n_planes == 8 || (n_planes > 0 && v.fmt != planes[0].w.fmt)) flush_planes(s);
-        planes[n_planes++] = DequantJob{v, rows, cols, out};
-    }
-    void flush_planes(hipStream_t s) {
-        if (n_planes > 0) launch_dequant_bf16_batch(planes, n_planes, s);
-        n_planes = 0;
-    }
-    void flush(hipStream_t s) {
-        flush_planes(s);
-        if (!blocks.empty()) launch_dequant_blocks(blocks.data(), (int)blocks.size(), s);
-        blocks.clear();
-    }
-};
-void expand_weight(const WeightView& v, int rows, int cols, uint16_t* out, hipStream_t s) {
-    Expander e;
-    e.add(v, rows, cols, out, s);
-    e.flush(s);
-}
-}  // namespace
-
-// Whether the layer loop multiplies the staged bf16 image of a matrix of this format: every quantized format by
-// default; with ACE_MI_QUANT_STAGED=0 only raw ggml blocks, which no dequant-fused GEMM reads.
-bool DitEngine::stages(int fmt) const { return staged_quant_ ? weight_quantized(fmt) : fmt == WF_GGML_RAW; }
-
-// The six block matrices of layer li: views of the bf16 staging slot (staged) or of the resident weights.
-DitEngine::LayerViews DitEngine::layer_views(int li, bool staged) {
-    const DevLayer& ly = model_.layers[li];
-    const DevWeight* ws[6] = {&ly.w_qkv, &ly.w_o, &ly.w_cq, &ly.w_co, &ly.w_gu, &ly.w_down};
-    WeightView v[6];
-    char* base = staged ? stage_slot(li) : nullptr;
-    size_t off = 0;
-    for (int i = 0; i < 6; ++i) {
-        v[i] = ws[i]->view();
-        if (lora_view(*ws[i], v[i])) {  // the adapted image in place of the resident / staged weights
-        } else if (staged && stages(ws[i]->fmt)) {
-            v[i].fmt = WF_BF16;
-            v[i].q = base + off;
-            v[i].s = nullptr;
-            v[i].ld = ws[i]->cols;
-        }
-        off += wbytes(*ws[i]);
-    }
-    return LayerViews{v[0], v[1], v[2], v[3], v[4], v[5]};
-}
-
-void DitEngine::stage_layer(int li, hipStream_t st) {
-    const DevLayer& ly = model_.layers[li];
-    const DevWeight* ws[6] = {&ly.w_qkv, &ly.w_o, &ly.w_cq, &ly.w_co, &ly.w_gu, &ly.w_down};
-    char* base = stage_slot(li);
-    size_t off = 0;
-    Expander ex;
-    tic(st);
-    for (int i = 0; i < 6; ++i) {
-        WeightView adapted;
-        if (stages(ws[i]->fmt) && ws[i]->q && !lora_view(*ws[i], adapted))  // (adapted: never read)
-            ex.add(ws[i]->view(), ws[i]->rows, ws[i]->cols, reinterpret_cast<uint16_t*>(base + off), st);
-        off += wbytes(*ws[i]);
-    }
-    ex.flush(st);
-    toc("dequant_stage", st);
-    images_written_ = true;
-}
-
-WeightView DitEngine::dense_view(const DevWeight& w, hipStream_t s) {
-    WeightView v = w.view();
-    if (lora_view(w, v)) return v;
-    // (a raw-block matrix always gets its image, in every scope: no GEMM reads the blocks)
-    if (v.fmt != WF_GGML_RAW && (!staged_quant_ || !stage_per_call_ || !weight_quantized(v.fmt))) return v;
-    if (!v.q) return v;
-    Buf& b = img_[v.q];
-    if (!b.p) {
-        ensure(b, (size_t)w.rows * w.cols * 2);
-        expand_weight(v, w.rows, w.cols, static_cast<uint16_t*>(b.p), s);
-        images_written_ = true;
-    }
-    v.fmt = WF_BF16;
-    v.q = b.p;
-    v.s = nullptr;
-    v.ld = w.cols;
-    return v;
-}
-
-// Side-stream sweep of layer li's block weights (ACE_MI_WEIGHT_PREFETCH), ordered after the work already queued
-// on s; the forward joins the side stream before it returns.
-void DitEngine::prefetch_layer(int li, bool staged, hipStream_t s) {
+// Side-stream sweep of the 16-bit images layer li's GEMMs will read (ACE_MI_WEIGHT_PREFETCH), ordered after the work
+// already queued on s; the forward joins the side stream before it returns.
+void DitEngine::prefetch_layer(int li, hipStream_t s) {
     if (!pf_stream_) {
         ACEMI_HIP(hipStreamCreateWithFlags(&pf_stream_, hipStreamNonBlocking));
         ACEMI_HIP(hipEventCreateWithFlags(&pf_ev_, hipEventDisableTiming));
         ACEMI_HIP(hipEventCreateWithFlags(&pf_done_, hipEventDisableTiming));
     }
     ensure(pf_sink_, 256);
-    const LayerViews lw = layer_views(li, staged);
-    const DevLayer& ly = model_.layers[li];
-    const DevWeight* ws[6] = {&ly.w_qkv, &ly.w_o, &ly.w_cq, &ly.w_co, &ly.w_gu, &ly.w_down};
-    const WeightView* vs[6] = {&lw.qkv, &lw.o, &lw.cq, &lw.co, &lw.gu, &lw.down};
-    const void* ptrs[6];
-    size_t bytes[6];
+    const LayerViews lw = images_.views(li);
+    const auto ws = model_.layers[li].block_weights();
+    const void* ptrs[N_BLOCK_WEIGHTS];
+    size_t bytes[N_BLOCK_WEIGHTS];
     int n = 0;
-    for (int i = 0; i < 6; ++i) {
-        if (weight_quantized(vs[i]->fmt) || !vs[i]->q) continue;  // bf16 / fp16 images only
-        ptrs[n] = vs[i]->q;
-        bytes[n] = (size_t)ws[i]->rows * ws[i]->cols * 2;
-        ++n;
+    for (int i = 0; i < N_BLOCK_WEIGHTS; ++i) {
+        if (weight_quantized(lw[i].fmt) || !lw[i].q) continue;  // bf16 / fp16 images only
+        ptrs[n] = lw[i].q;
+        bytes[n++] = WeightImages::wbytes(*ws[i]);
     }
     if (n == 0) return;
     ACEMI_HIP(hipEventRecord(pf_ev_, s));
     ACEMI_HIP(hipStreamWaitEvent(pf_stream_, pf_ev_, 0));
     launch_prefetch(ptrs, bytes, n, prefetch_blocks_, get<unsigned>(pf_sink_), pf_stream_);
-}
-
-// Layer li's bf16 image: its own slot when the images of the whole model are kept for the sampling call,
-// else the single slot every layer shares.
-char* DitEngine::stage_slot(int li) {
-    return static_cast<char*>(wring_.p) + (stage_per_call_ ? (size_t)li * stage_slot_bytes_ : 0);
 }
 
 // Device table of every layer's cross-attention k-norm weights (PrepArgs::k_norm_layers), built once.
@@ -204,24 +79,6 @@ const float* const* DitEngine::cross_norm_table() {
         knorm_tab_n_ = n;
     }
     return static_cast<const float* const*>(knorm_tab_.p);
-}
-
-void DitEngine::ensure(Buf& b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return;
-    if (b.p) {
-        ACEMI_HIP(hipDeviceSynchronize());
-        ACEMI_HIP(hipFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
-    }
-    const size_t alloc = (bytes + 255) & ~size_t(255);
-    ACEMI_HIP(hipMalloc(&b.p, alloc));
-    ACEMI_HIP(hipMemset(b.p, 0, alloc));
-    // hipMemset runs on the legacy null stream, which does not order against the library's
-    // non-blocking streams: finish it before any kernel can write the new buffer
-    ACEMI_HIP(hipDeviceSynchronize());
-    b.bytes = alloc;
 }
 
 void DitEngine::set_profiling(bool on) {
@@ -368,14 +225,13 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
                     "quantized-activation mode: F32 proj_in / proj_out (GGUF) are not supported");
     prepare_shape(B, Np, L);
     rope_for(Np, s);
-    // bf16 images written by an earlier forward (possibly on another stream) are complete before this one reads them
-    if (stage_ev_set_) ACEMI_HIP(hipStreamWaitEvent(s, stage_ev_, 0));
-    images_written_ = false;
     // parity: the cross K/V planes below are this mode's (f32 precision), not the cached ones
     if constexpr (QACT) cross_key_.valid = false;
 
     int n_layers = c.layers;
     if (io.max_layers > 0) n_layers = std::min(n_layers, io.max_layers);
+    // the product reads weight images (weight_images.h); parity multiplies the resident weights: nothing staged
+    images_.begin_forward(QACT ? 0 : n_layers, io.reuse_stage, s);
     const int Kin = kin * P * c.in_channels;
 
     float* x = get<float>(x_);
@@ -392,7 +248,7 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
     }
 
     // ---- the seam
-    auto weight = [&](const DevWeight& w) { return QACT ? w.view() : dense_view(w, s); };
+    auto weight = [&](const DevWeight& w) { return QACT ? w.view() : images_.matrix(w, s); };
     auto linear = [&](const Row* in, int ld, int rows, const WeightView& w, int N, int K, const GemmEpilogue& e,
                       const char* name) {
         if constexpr (QACT) {
@@ -479,8 +335,7 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
             encp = get<uint16_t>(encp_);
             tic(s);
             launch_to_act(at, io.enc, (int64_t)Me * H, false, get<uint16_t>(enc_act_), s);
-            launch_gemm(get<uint16_t>(enc_act_), H, dense_view(m.cond_w, s), Me, H, H, epi_store_act(encp, H, m.cond_b),
-                        s);
+            launch_gemm(get<uint16_t>(enc_act_), H, weight(m.cond_w), Me, H, H, epi_store_act(encp, H, m.cond_b), s);
             toc("gemm_condition", s);
         }
         // one GEMM for every layer's cross k|v when the weights are fused: ckv [Me][n_layers*2kd]; the product then
@@ -508,36 +363,12 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
     const float* mods = get<float>(mods_);
     const int64_t mstride = 6LL * H;  // per item within a layer
 
-    // staged dequant (product): each layer's quantized block matrices are expanded to their bf16 image right before
-    // the layer, in stream order, into one workspace slot (see engine.h)
-    bool any_raw = false;  // (raw blocks are staged whatever ACE_MI_QUANT_STAGED says: stages())
-    for (int li = 0; li < n_layers; ++li) {
-        const DevLayer& ly = m.layers[li];
-        for (const DevWeight* w : {&ly.w_qkv, &ly.w_o, &ly.w_cq, &ly.w_co, &ly.w_gu, &ly.w_down})
-            any_raw = any_raw || w->fmt == WF_GGML_RAW;
-    }
-    const bool staged =
-        !QACT && n_layers > 0 && ((staged_quant_ && weight_quantized(m.layers[0].w_gu.fmt)) || any_raw);
-    bool restage = true;
-    if (staged) {
-        const DevLayer& l0 = m.layers[0];
-        stage_slot_bytes_ = wbytes(l0.w_qkv) + wbytes(l0.w_o) + wbytes(l0.w_cq) + wbytes(l0.w_co) +
-                            wbytes(l0.w_gu) + wbytes(l0.w_down);
-        ensure(wring_, stage_slot_bytes_ * (stage_per_call_ ? n_layers : 1));
-        // per-call scope: the images written by the first forward of a sampling call serve its later steps
-        // (the weights are loop-invariant); any other forward expands them again
-        // "model" scope: the images stay valid across calls (the weights never change after load), so the
-        // reference's per-step decoder.forward hook does not re-expand them either
-        restage = !(stage_per_call_ && (io.reuse_stage || stage_model_) && stage_layers_ >= n_layers);
-        stage_layers_ = stage_per_call_ ? n_layers : 0;
-    }
-
     for (int li = 0; li < n_layers; ++li) {  // :1466-1535
         const DevLayer& ly = m.layers[li];
-        if (staged && restage) stage_layer(li, s);
-        if (!QACT && prefetch_blocks_ > 0 && li + 1 < n_layers && !(staged && restage))
-            prefetch_layer(li + 1, staged, s);
-        const LayerViews lw = layer_views(li, staged);  // (not staged: the resident weights)
+        if (images_.expanding()) tic(s);
+        const LayerViews lw = images_.layer(li, s);  // (expands the layer's images first when this forward does)
+        if (images_.expanding()) toc("dequant_stage", s);
+        if (!QACT && prefetch_blocks_ > 0 && li + 1 < n_layers && !images_.expanding()) prefetch_layer(li + 1, s);
         const float* lm = mods + (size_t)li * B * 6 * H;
         const float* shift_msa = lm + 0 * H;
         const float* scale_msa = lm + 1 * H;
@@ -548,30 +379,30 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
 
         // self-attention block: the QKV projection with QK-RMSNorm, RoPE and the attention re-layout in its epilogue
         norm(at, ly.self_norm, scale_msa, shift_msa, mstride, act, false);
-        project(lw.qkv, qd + 2 * kd,
+        project(lw[BW_QKV], qd + 2 * kd,
                 self_prep(dims, planes, nullptr, 0, ly.sq_norm, ly.sk_norm, get<float>(cos_), get<float>(sin_),
                           get<uint16_t>(qh_), get<uint16_t>(kh_), get<uint16_t>(vt_)),
                 "gemm_qkv");
         attention(get<uint16_t>(kh_), get<uint16_t>(vt_), io.mask ? get<float>(kbias_) : nullptr, Np, Npad,
                   dims.k_plane(), ly.sliding ? std::max(c.sliding_window, 0) : 0,  // padding keys: masked in-kernel
                   ly.sliding ? "attn_self_sliding" : "attn_self_full");
-        linear(attn, qd, M, lw.o, H, qd, epi_resid_gated(x, H, gate_msa, mstride, Np), "gemm_o");
+        linear(attn, qd, M, lw[BW_O], H, qd, epi_resid_gated(x, H, gate_msa, mstride, Np), "gemm_o");
         if (!QACT && li == fault_.layer)  // TEST ONLY: the injected fault must reach the norm that follows
             launch_fault_tile(x, H, M, fault_.row, fault_.col, fault_.amp, s);
 
         // cross-attention block (:1502-1520): no AdaLN, no gate, no RoPE
         if (ly.cross && L > 0) {
             norm(at, ly.cross_norm, nullptr, nullptr, 0, act, false);
-            project(lw.cq, qd, cross_q_prep(dims, planes, ly.cq_norm, get<uint16_t>(qh_)), "gemm_cross_q");
+            project(lw[BW_CQ], qd, cross_q_prep(dims, planes, ly.cq_norm, get<uint16_t>(qh_)), "gemm_cross_q");
             attention(get<uint16_t>(kc_) + li * kc_layer, get<uint16_t>(vc_) + li * kc_layer,
                       io.enc_mask ? get<float>(kbias_c_) : nullptr, L, Lpad, kc_plane, 0, "attn_cross");
-            linear(attn, qd, M, lw.co, H, qd, epi_resid(x, H), "gemm_cross_o");
+            linear(attn, qd, M, lw[BW_CO], H, qd, epi_resid(x, H), "gemm_cross_o");
         }
 
         // MLP block (:1522-1534); parity's SwiGLU rows overwrite their own (already quantized) input
         norm(at, ly.mlp_norm, c_scale, c_shift, mstride, act, false);
-        linear(act, H, M, lw.gu, 2 * I, H, epi_swiglu(act2, I), "gemm_gate_up");
-        linear(act2, I, M, lw.down, H, I, epi_resid_gated(x, H, c_gate, mstride, Np), "gemm_down");
+        linear(act, H, M, lw[BW_GU], 2 * I, H, epi_swiglu(act2, I), "gemm_gate_up");
+        linear(act2, I, M, lw[BW_DOWN], H, I, epi_resid_gated(x, H, c_gate, mstride, Np), "gemm_down");
     }
 
     // ---- output head (:1537-1559)
@@ -582,11 +413,7 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
         linear(head_in, kout * H, M, weight(m.proj_out_w), P * c.audio_dim, kout * H,
                epi_proj_out(io.out, m.proj_out_b, Np, T, c.audio_dim, P), "gemm_proj_out");
     }
-    if (images_written_) {
-        if (!stage_ev_) ACEMI_HIP(hipEventCreateWithFlags(&stage_ev_, hipEventDisableTiming));
-        ACEMI_HIP(hipEventRecord(stage_ev_, s));
-        stage_ev_set_ = true;
-    }
+    images_.end_forward(s);
     if (pf_stream_) {  // the side stream's sweeps end before anything ordered after this forward on s
         ACEMI_HIP(hipEventRecord(pf_done_, pf_stream_));
         ACEMI_HIP(hipStreamWaitEvent(s, pf_done_, 0));
@@ -709,28 +536,15 @@ void DitEngine::probe_gemm(int which, int M, int iters, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- LoRA adapters (engine.h)
-bool DitEngine::lora_view(const DevWeight& w, WeightView& v) const {
-    if (!lora_active_ || !w.q) return false;
-    const auto it = lora_img_.find(w.q);
-    if (it == lora_img_.end() || !it->second.p) return false;
-    v.fmt = weight_quantized(w.fmt) ? WF_BF16 : w.fmt;
-    v.q = it->second.p;
-    v.s = nullptr;
-    v.ld = w.cols;
-    return true;
-}
-
 void DitEngine::free_lora() {
-    for (auto& kv : lora_img_)
-        if (kv.second.p) (void)hipFree(kv.second.p);
-    lora_img_.clear();
+    images_.adapted.clear();
+    images_.adapter_on = false;
     if (lora_ab_) (void)hipFree(lora_ab_);
     lora_ab_ = nullptr;
     lora_a_.clear();
     lora_b_.clear();
     lora_.reset();
     lora_scale_ = 0.f;
-    lora_active_ = false;
     lora_merge_ms_ = 0.0;
 }
 
@@ -743,7 +557,7 @@ DitEngine::LoraInfo DitEngine::lora_info() const {
     i.min_rank = lora_->min_rank;
     i.max_rank = lora_->max_rank;
     i.modules = (int)lora_->modules.size();
-    for (const auto& kv : lora_img_)
+    for (const auto& kv : images_.adapted)
         if (kv.second.p) {
             ++i.images;
             i.image_bytes += kv.second.bytes;
@@ -753,13 +567,13 @@ DitEngine::LoraInfo DitEngine::lora_info() const {
 }
 
 // The images of the current adapter at the current scale, always from the base weights.  Everything that was
-// computed from the previous views goes: the cached cross K/V and the staged slots (stage_layer leaves the slot of
-// an adapted matrix unwritten, so the next forward expands them again).
+// computed from the previous views goes: the cached cross K/V and the staged slots (an adapted matrix's slot is left
+// unwritten, so the next forward expands them again).
 void DitEngine::rebuild_lora_images(hipStream_t s) {
     ACEMI_HIP(hipDeviceSynchronize());  // a forward in flight (on any stream) reads the current views
     cross_key_.valid = false;
-    stage_layers_ = 0;
-    lora_active_ = false;
+    images_.invalidate();
+    images_.adapter_on = false;
     lora_merge_ms_ = 0.0;
     if (!lora_ || lora_scale_ == 0.f) return;
 
@@ -815,23 +629,24 @@ void DitEngine::rebuild_lora_images(hipStream_t s) {
 
     // allocate first (ensure() synchronises the device), then launch everything in stream order
     std::vector<LoraMergeJob> jobs;
-    std::vector<const DevWeight*> expand;
+    std::vector<std::pair<const DevWeight*, uint16_t*>> expand;
     for (const auto& mt : mats) {
         const DevWeight& w = *mt.first;
         bool any = false;
         for (const Slot& sl : mt.second) any = any || sl.mod >= 0;
         if (!any) continue;
         ACEMI_CHECK(w.q && w.fmt != WF_F32X3, "lora: the targeted weight is not a 16-bit or block-format matrix");
-        Buf& img = lora_img_[w.q];
-        ensure(img, (size_t)w.rows * w.cols * 2);
+        Buf& buf = images_.adapted[w.q];
+        ensure(buf, WeightImages::wbytes(w));
+        uint16_t* img = static_cast<uint16_t*>(buf.p);
         const bool quantized = weight_quantized(w.fmt);
-        if (quantized) expand.push_back(&w);
+        if (quantized) expand.emplace_back(&w, img);
         for (size_t k = 0; k < mt.second.size(); ++k) {
             const Slot& sl = mt.second[k];
             LoraMergeJob j;
             j.fmt = quantized ? WF_BF16 : w.fmt;
-            j.base = quantized ? static_cast<const uint16_t*>(img.p) : static_cast<const uint16_t*>(w.q);
-            j.out = static_cast<uint16_t*>(img.p);
+            j.base = quantized ? img : static_cast<const uint16_t*>(w.q);
+            j.out = img;
             j.ld_base = j.ld_out = w.cols;
             j.cols = w.cols;
             j.map = sl.map;
@@ -864,12 +679,11 @@ void DitEngine::rebuild_lora_images(hipStream_t s) {
     }
     ACEMI_HIP(hipDeviceSynchronize());
     const auto t0 = std::chrono::steady_clock::now();
-    for (const DevWeight* w : expand)
-        expand_weight(w->view(), w->rows, w->cols, static_cast<uint16_t*>(lora_img_[w->q].p), s);
+    for (const auto& e : expand) WeightImages::expand(*e.first, e.second, s);
     launch_lora_merge(jobs.data(), (int)jobs.size(), s);
     ACEMI_HIP(hipStreamSynchronize(s));
     lora_merge_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    lora_active_ = true;
+    images_.adapter_on = true;
 }
 
 void DitEngine::load_lora(const std::string& dir, float scale, int max_layers, hipStream_t s) {

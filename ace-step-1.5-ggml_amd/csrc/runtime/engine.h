@@ -15,6 +15,7 @@
 #include "../kernels.h"
 #include "blocks.h"
 #include "model.h"
+#include "weight_images.h"
 
 namespace acemi {
 
@@ -100,12 +101,11 @@ class DitEngine {
     void reset_times();
     // launch only the MLP gate/up GEMM of layer 0 for a given M (bench / roofline probe)
     void probe_gemm(int which, int M, int iters, hipStream_t s);
-    // PEFT LoRA adapter (runtime/lora.h reads it): every fused block matrix / the cross k|v matrix that holds a
-    // targeted module gets an adapted 16-bit image rne16(W + eff * B.A) (launch_lora_merge; a quantized matrix is
-    // expanded to its bf16 image first and merged in place), and layer_views / dense_view hand that image to the
-    // GEMMs in place of the resident or staged weights: same kernels, same launches, nothing per step.  The base
-    // weights are never written, so a scale change rebuilds from them and unload is exact.  All three block until
-    // the device is idle (a forward in flight reads the current views).  max_layers: ACE_GGML_DIT_MAX_LAYERS.
+    // PEFT LoRA adapter (runtime/lora.h reads it): every fused block matrix / the cross k|v
+    // matrix that holds a targeted module gets an adapted 16-bit image (launch_lora_merge; a quantized matrix is
+    // expanded to its bf16 image first and merged in place), which the GEMMs read from then on (weight_images.h): same
+    // kernels, same launches, nothing per step.  A scale change rebuilds from the base weights and unload is exact.
+    // All three block until the device is idle.  max_layers: ACE_GGML_DIT_MAX_LAYERS.
     struct LoraInfo {
         bool loaded = false;
         float scale = 0.f, lora_alpha = 0.f;
@@ -120,11 +120,6 @@ class DitEngine {
     LoraInfo lora_info() const;
 
    private:
-    struct Buf {
-        void* p = nullptr;
-        size_t bytes = 0;
-    };
-    void ensure(Buf& b, size_t bytes);
     template <typename T>
     T* get(Buf& b) {
         return static_cast<T*>(b.p);
@@ -181,52 +176,15 @@ class DitEngine {
                  const char* name, hipStream_t s, bool silu_in = false);
     void timestep_embed_qact(const float* t, const float* r, int rows, float* proj, float* temb_t, float* temb_r,
                              hipStream_t s);
-    // Staged dequant of quantized block weights (ACE_MI_QUANT_STAGED, default on; 0 = the dequant-fused GEMMs):
-    // right before each layer its Q8_0 / Q4_K / Q6_K matrices are expanded to their bf16 image
-    // (launch_dequant_bf16, bit-identical to the dequant-fused GEMM's LDS tiles) in one workspace slot, and
-    // the block GEMMs run the dense bf16 kernels.  In stream order: a side-stream ring overlapped with the
-    // previous layer gained nothing measurable (the GEMMs leave no CU resources for it) and, for Q4_K only,
-    // changed the results of the concurrently running layer (tools/diag_staged.py) — not understood, so
-    // not used.
-    struct LayerViews {
-        WeightView qkv, o, cq, co, gu, down;
-    };
-    // Scope of the staged images (ACE_MI_QUANT_STAGE_SCOPE): "model" (default since round 3) expands every layer's
-    // image once, at the first forward after the load, and keeps it while the weights are loaded (they never change),
-    // so the per-step decoder.forward hook and the ABI forward do not re-expand them either; "call" keeps one
-    // slot per layer for one sampling call (expanded at its step 0); both cost a bf16 image of the block weights
-    // as workspace (2.8 GB for the 24-layer DiT: 1 % of HBM); "layer" = the single shared 117 MB slot, expanded
-    // before every layer of every forward (the low-memory mode: weights + one slot).
-    bool staged_quant_ = true;
-    bool stage_per_call_ = true;
-    bool stage_model_ = true;  // images kept across calls while the weights are loaded (ACE_MI_QUANT_STAGE_SCOPE)
-    size_t stage_slot_bytes_ = 0;
-    int stage_layers_ = 0;  // layers whose images wring_ holds (per-call scope)
-    Buf wring_;
-    // bf16 images of the quantized weights outside the six block matrices (condition embedder, every layer's
-    // cross k|v, proj in / out), expanded at their first use and kept while the weights are loaded (model and
-    // call scope; the layer scope runs them through the dequant-fused GEMM)
-    std::map<const void*, Buf> img_;
-    // recorded after a forward that wrote bf16 images (staged slots or dense_view images); every later forward's
-    // stream waits on it, so a forward on another stream never reads an image still being expanded
-    hipEvent_t stage_ev_ = nullptr;
-    bool stage_ev_set_ = false;
-    bool images_written_ = false;
-    WeightView dense_view(const DevWeight& w, hipStream_t s);
-    bool stages(int fmt) const;  // the layer loop reads this format's staged image (raw ggml blocks: always)
-    char* stage_slot(int li);
-    LayerViews layer_views(int li, bool staged);
-    void stage_layer(int li, hipStream_t st);
-    // LoRA state: the adapter's A / B in one device buffer (lora_ab_), the adapted images keyed like img_ by the
-    // resident weight pointer; lora_active_ = an adapter is loaded at a non-zero scale (the views use the images)
+    // Which bytes a GEMM reads for a weight (resident, staged / kept bf16 image, adapted image): weight_images.h.
+    WeightImages images_{model_};
+    // LoRA state: the adapter's A / B in one device buffer (lora_ab_); the adapted images are in
+    // images_, read while an adapter is loaded at a non-zero scale
     std::unique_ptr<LoraAdapter> lora_;
     std::vector<const float*> lora_a_, lora_b_;  // device A / B of lora_->modules[i]
     void* lora_ab_ = nullptr;
     float lora_scale_ = 0.f;
-    bool lora_active_ = false;
     double lora_merge_ms_ = 0.0;
-    std::map<const void*, Buf> lora_img_;
-    bool lora_view(const DevWeight& w, WeightView& v) const;
     void rebuild_lora_images(hipStream_t s);
     void free_lora();
     struct Fault {  // ACE_MI_TEST_FAULT (test-only fault injection); layer -1 = off
@@ -240,7 +198,7 @@ class DitEngine {
     hipStream_t pf_stream_ = nullptr;
     hipEvent_t pf_ev_ = nullptr, pf_done_ = nullptr;
     Buf pf_sink_;
-    void prefetch_layer(int li, bool staged, hipStream_t s);
+    void prefetch_layer(int li, hipStream_t s);
     // profiling
     bool profiling_ = false;
     hipEvent_t ev0_ = nullptr, ev1_ = nullptr;

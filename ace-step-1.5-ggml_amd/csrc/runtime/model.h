@@ -10,6 +10,7 @@
 //   * norms, biases and AdaLN tables widened to f32 once (ggml cast_f32).
 #pragma once
 
+#include <array>
 #include <string>
 #include <vector>
 
@@ -75,7 +76,10 @@ struct DevLayer {
     float* ck_norm = nullptr;
     bool sliding = false;
     bool cross = true;  // Layer::use_cross_attention default
+    // the six matrices of the block's linears (w_ckv is applied outside the layer loop), indexed by BlockWeight
+    std::array<const DevWeight*, 6> block_weights() const { return {&w_qkv, &w_o, &w_cq, &w_co, &w_gu, &w_down}; }
 };
+enum BlockWeight : int { BW_QKV, BW_O, BW_CQ, BW_CO, BW_GU, BW_DOWN, N_BLOCK_WEIGHTS };
 
 // A condition encoder (ace_dit::Model lyric_* / timbre_*, acestep_dit_model.h; loaded at
 // acestep_dit_model.cpp:889-996): input projection (+ bias), Qwen-style blocks without AdaLN stored in

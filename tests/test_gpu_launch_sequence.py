@@ -35,6 +35,10 @@ MODES = {
     "d_quant_act_q8": ({"ACE_GGML_DIT_WEIGHT_QTYPE": "q8_0", "ACE_MI_QUANT_ACT": "q8"},
                        [("pack_input", 1), ("gemm_proj_in", 1), ("timestep_l1", 2), ("timestep_l2", 2),
                         ("timestep_proj", 2), ("gemm_condition", 1), ("gemm_cross_kv", 1), ("attn_prep", 2)] + LAYERS),
+    # (e) Q8_0 weights, defaults (staged dequant, model scope): the launches of (a) plus one expansion per layer, the
+    # first of them right before layer 0's first norm (WeightImages::layer at the top of the layer loop)
+    "e_q8_0_staged": ({"ACE_GGML_DIT_WEIGHT_QTYPE": "q8_0"},
+                      PRODUCT_HEAD + [("attn_prep", 1), ("dequant_stage", 2)] + LAYERS),
 }
 
 
@@ -58,7 +62,8 @@ def profile(br):
 def test_forward_launch_sequence(tiny_ckpt, monkeypatch, mode):
     from acestep_mi355x.capi import GGMLCAPIBridge
     env, expected = MODES[mode]
-    for k in ("ACE_MI_UNFUSED_PREP", "ACE_GGML_DIT_WEIGHT_QTYPE", "ACE_MI_QUANT_STAGED", "ACE_MI_QUANT_ACT"):
+    for k in ("ACE_MI_UNFUSED_PREP", "ACE_GGML_DIT_WEIGHT_QTYPE", "ACE_MI_QUANT_STAGED", "ACE_MI_QUANT_ACT",
+              "ACE_MI_QUANT_STAGE_SCOPE"):
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
