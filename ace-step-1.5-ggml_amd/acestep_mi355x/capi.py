@@ -42,6 +42,7 @@ EXPORTED_SYMBOLS = (
     "ace_ggml_text_encoder_forward_masked", "ace_ggml_text_encoder_forward_embeddings",
     "ace_ggml_text_encoder_forward_layers", "ace_ggml_generate_audio_simple", "ace_ggml_generate_audio_style_lyric_simple",
     "ace_ggml_generate_audio_style_lyric_timbre_simple", "ace_mi_reference_noise",
+    "ace_mi_load_lm", "ace_mi_lm_get_info", "ace_mi_lm_begin", "ace_mi_lm_forward", "ace_mi_lm_reset",
 )
 
 # Every symbol declared in include/acestep_mi355x_selftest.h: the TEST library (libacestep_mi355x_selftest.so = the
@@ -86,6 +87,13 @@ class AceMiLoraInfo(ctypes.Structure):
     _fields_ = [("loaded", ctypes.c_int32), ("scale", ctypes.c_float), ("lora_alpha", ctypes.c_float),
                 ("min_rank", ctypes.c_int32), ("max_rank", ctypes.c_int32), ("num_modules", ctypes.c_int32),
                 ("num_images", ctypes.c_int32), ("image_bytes", ctypes.c_int64), ("merge_ms", ctypes.c_double)]
+
+
+class AceMiLmInfo(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "vocab_size", "hidden_size", "num_layers", "num_heads", "num_kv_heads", "head_dim", "max_positions", "tied",
+        "act_type", "batch", "capacity", "cache_len")] + [("weight_bytes", ctypes.c_int64),
+                                                          ("cache_bytes", ctypes.c_int64)]
 
 
 class AceMiBlockSeg(ctypes.Structure):
@@ -218,6 +226,19 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ace_mi_timbre_encode.restype = ctypes.c_int
     lib.ace_mi_build_condition.argtypes = [vp, fp, i32, fp, i32, i32, fp, ip, i32, i32, fp, sz, ip, sz, ip]
     lib.ace_mi_build_condition.restype = ctypes.c_int
+    # the LM entries live in their own translation unit (runtime/lm.cpp); a host-emulation library built without it
+    # (tests/hostlib.py) has none of them, and the bridge's lm_* methods then fail on the missing symbol
+    if hasattr(lib, "ace_mi_load_lm"):
+        lib.ace_mi_load_lm.argtypes = [vp, ctypes.c_char_p]
+        lib.ace_mi_load_lm.restype = ctypes.c_int
+        lib.ace_mi_lm_get_info.argtypes = [vp, ctypes.POINTER(AceMiLmInfo)]
+        lib.ace_mi_lm_get_info.restype = ctypes.c_int
+        lib.ace_mi_lm_begin.argtypes = [vp, i32, i32]
+        lib.ace_mi_lm_begin.restype = ctypes.c_int
+        lib.ace_mi_lm_forward.argtypes = [vp, vp, vp, i32, vp, vp]
+        lib.ace_mi_lm_forward.restype = ctypes.c_int
+        lib.ace_mi_lm_reset.argtypes = [vp]
+        lib.ace_mi_lm_reset.restype = ctypes.c_int
     if path is None:
         _LIB = lib
     return lib
@@ -427,6 +448,49 @@ class GGMLCAPIBridge:
         else:
             st = self.lib.ace_ggml_text_encoder_forward(self.ctx, _iptr(ids), ids.shape[0], _fptr(out), out.nbytes)
         self._ensure_ok(st, "ace_ggml_text_encoder_forward")
+        return out
+
+    # -- the 5 Hz causal LM with its KV cache (include/acestep_mi355x.h ace_mi_load_lm / ace_mi_lm_*) -----------
+    def load_lm(self, model_dir) -> None:
+        """A HF Qwen3ForCausalLM directory into the LM slot (the text encoder stays resident beside it)."""
+        self._ensure_ok(self.lib.ace_mi_load_lm(self.ctx, str(model_dir).encode("utf-8")), "ace_mi_load_lm")
+
+    def lm_info(self) -> dict:
+        info = AceMiLmInfo()
+        self._ensure_ok(self.lib.ace_mi_lm_get_info(self.ctx, ctypes.byref(info)), "ace_mi_lm_get_info")
+        return {n: int(getattr(info, n)) for n, _ in AceMiLmInfo._fields_}
+
+    def lm_begin(self, batch: int, capacity: int) -> None:
+        self._ensure_ok(self.lib.ace_mi_lm_begin(self.ctx, int(batch), int(capacity)), "ace_mi_lm_begin")
+
+    def lm_reset(self) -> None:
+        self._ensure_ok(self.lib.ace_mi_lm_reset(self.ctx), "ace_mi_lm_reset")
+
+    def lm_forward_device(self, d_ids: int, d_mask: int, n: int, d_logits: int, stream: int = 0) -> None:
+        st = self.lib.ace_mi_lm_forward(self.ctx, d_ids, d_mask or None, int(n), d_logits, stream or None)
+        self._ensure_ok(st, "ace_mi_lm_forward")
+
+    def lm_forward(self, input_ids, attention_mask=None):
+        """Append input_ids [B, n] (torch tensor on the engine's device; attention_mask [B, n] for the same columns,
+        or None) and return the last position's logits as an f32 [B, vocab] tensor on that device, in stream
+        order on torch's current stream (the stream rules of hook.dit_forward_torch)."""
+        import torch
+        from .hook import _OrderedCall
+        ids = input_ids.detach().to(torch.int32).contiguous()
+        if ids.dim() != 2:
+            raise ValueError("lm_forward: input_ids must be [B, n]")
+        dev = ids.device
+        am = None
+        if attention_mask is not None:
+            am = (attention_mask.detach().to(dev) != 0).to(torch.int32).contiguous()
+            if am.shape != ids.shape:
+                raise ValueError("lm_forward: attention_mask must cover exactly the appended columns")
+        if getattr(self, "_lm_vocab", None) is None:
+            self._lm_vocab = self.lm_info()["vocab_size"]
+        out = torch.empty((ids.shape[0], self._lm_vocab), dtype=torch.float32, device=dev)
+        with _OrderedCall(self, dev) as stream:
+            self.lm_forward_device(ids.data_ptr(), am.data_ptr() if am is not None else 0, ids.shape[1],
+                                   out.data_ptr(), stream)
         return out
 
     # reference GGMLCAPIBridge names (scripts/run_non_ggml_real_case.py:255-281)

@@ -300,6 +300,93 @@ def install_vae_backend(dit_handler: Any, bridge, chunk_size_default: int = 32, 
     setattr(dit_handler, "_ggml_vae_backend", "mi355x-capi")
 
 
+class _LmOutput:
+    """What the reference loops read of a CausalLMOutputWithPast: .logits and .past_key_values."""
+
+    def __init__(self, logits, past_key_values):
+        self.logits = logits
+        self.past_key_values = past_key_values
+
+
+class _LmCacheHandle:
+    """Opaque past_key_values: the cache itself lives in the engine; only the newest handle is live."""
+
+    def __init__(self, serial: int):
+        self.serial = serial
+        self.length = 0
+
+    def get_seq_length(self, *a, **kw) -> int:
+        return self.length
+
+
+class _GenerationConfig:
+    use_cache = True
+
+
+class EngineCausalLM:
+    """`llm_handler.llm` drop-in for the reference's `pt` backend (acestep/llm_inference.py:345-367, :2259-2471): the
+    two custom loops only ever call `model(input_ids=..., attention_mask=..., past_key_values=..., use_cache=...)` and
+    read `.logits[:, -1, :]` and `.past_key_values`.  The engine supplies the logits (ace_mi_lm_forward); the
+    constrained-decoding FSM, CFG mixing and sampling stay in the reference's Python."""
+
+    def __init__(self, bridge, device=None, max_new_tokens: int = 4096):
+        import torch
+        self.bridge = bridge
+        self.info = bridge.lm_info()
+        self.device = torch.device(device if device is not None else "cuda")
+        self.generation_config = _GenerationConfig()
+        self.max_new_tokens = int(max_new_tokens)
+        self._live = None
+        self._serial = 0
+
+    def eval(self):
+        return self
+
+    def to(self, *a, **kw):
+        return self
+
+    def generate(self, *a, **kw):
+        raise NotImplementedError("the engine-backed LM serves the reference's custom loops "
+                                  "_generate_with_constrained_decoding and _generate_with_cfg_custom; "
+                                  "transformers' generate() is not supported")
+
+    def __call__(self, input_ids=None, attention_mask=None, past_key_values=None, use_cache=True, **kw):
+        if input_ids is None or input_ids.dim() != 2:
+            raise ValueError("input_ids must be a [B, n] tensor")
+        B, n = int(input_ids.shape[0]), int(input_ids.shape[1])
+        if past_key_values is None:
+            cap = min(self.info["max_positions"], n + self.max_new_tokens)
+            self.bridge.lm_begin(B, cap)
+            self._serial += 1
+            self._live = _LmCacheHandle(self._serial)
+        else:
+            if past_key_values is not self._live:
+                raise ValueError("stale past_key_values: the engine holds one KV cache, that of the newest prefill")
+            if n != 1:
+                raise ValueError("with past_key_values the engine decodes one token per call: input_ids must be [B, 1]")
+        mask = None
+        if attention_mask is not None:  # the loops pass the whole grown mask; the engine wants the appended columns
+            if attention_mask.shape[-1] < n:
+                raise ValueError("attention_mask is shorter than input_ids")
+            mask = attention_mask[:, attention_mask.shape[-1] - n:]
+        logits = self.bridge.lm_forward(input_ids, mask)
+        self._live.length += n
+        return _LmOutput(logits[:, None, :], self._live)
+
+    forward = __call__
+
+
+def install_lm_backend(llm_handler: Any, bridge, max_new_tokens: int = 4096) -> None:
+    """Point the reference LLM handler's `pt` backend at the engine: `llm_handler.llm` becomes an EngineCausalLM over
+    the LM that `bridge.load_lm` loaded (needs no `transformers`)."""
+    device = getattr(llm_handler, "device", None)
+    if device is None or str(device) in ("auto", "cpu"):
+        device = "cuda"
+    llm_handler.llm = EngineCausalLM(bridge, device=device, max_new_tokens=max_new_tokens)
+    llm_handler.llm_backend = "pt"
+    setattr(llm_handler, "_ggml_lm_backend", "mi355x-capi")
+
+
 def install_text_encoder_backend(dit_handler: Any, bridge) -> None:
     """`_install_ggml_text_encoder_backend` (scripts/run_non_ggml_real_case.py:406-428): route
     `dit_handler.infer_text_embeddings` / `infer_lyric_embeddings` through the GPU text encoder

@@ -162,6 +162,24 @@ def text_tensor_specs(cfg: dict) -> Iterator[Tuple[str, Tuple[int, ...], str]]:
         yield p + "mlp.down_proj.weight", (H, I), "w"
 
 
+def lm_tensor_specs(cfg: dict, tied: bool = True, model_prefix: bool = True):
+    """A HF Qwen3ForCausalLM state dict: the text model's tensors under "model." and, untied, lm_head.weight."""
+    for name, shape, kind in text_tensor_specs(cfg):
+        yield ("model." if model_prefix else "") + name, shape, kind
+    if not tied:
+        yield "lm_head.weight", (cfg["vocab_size"], cfg["hidden_size"]), "w"
+
+
+def write_lm_checkpoint(out_dir: str, cfg: Optional[dict] = None, seed: int = 7, tied: bool = True, dtype: str = "BF16",
+                        model_prefix: bool = True, std: float = 0.02) -> str:
+    """config.json + model.safetensors of a tiny causal LM (the 5 Hz LM's format: Qwen3ForCausalLM) built on
+    TEXT_TINY_CONFIG / text_tensor_specs; `tied` leaves lm_head.weight out and sets tie_word_embeddings."""
+    cfg = dict(TEXT_TINY_CONFIG if cfg is None else cfg, architectures=["Qwen3ForCausalLM"],
+               tie_word_embeddings=bool(tied))
+    return write_checkpoint(out_dir, cfg, seed=seed, dtype=dtype, std=std,
+                            specs=lm_tensor_specs(cfg, tied=tied, model_prefix=model_prefix))
+
+
 def write_checkpoint(out_dir: str, cfg: dict, seed: int = 0, dtype: str = "BF16", std: float = 0.02,
                      backend: str = "numpy", specs=None, qk_norm_scale: float = 1.0,
                      qk_norm_tags=("self_attn", "cross_attn")) -> str:

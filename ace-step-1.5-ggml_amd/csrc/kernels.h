@@ -350,6 +350,63 @@ void launch_prefetch(const void* const* ptrs, const size_t* bytes, int n, int bl
 // SDE re-noise step: xt = t_next * noise + (1 - t_next) * (xt - v * t)
 void launch_sde(float* xt, const float* v, const float* noise, int64_t n, float t, float t_next, hipStream_t s);
 
+// ------------------------------------------------------------ LM decode step (kernels/lm_decode.hip)
+// The M = 1..8 regime of the causal LM's token-by-token decode (runtime/lm.cpp): HBM-bound, no MFMA.
+constexpr int LM_MAX_BATCH = 8;
+// keys per decode-attention workgroup; a step over more keys splits into ranges of this size and merges them
+constexpr int LM_SPLIT_KEYS = 256;
+enum LmEpi : int {
+    LM_EPI_STORE = 0,   // y_f32[b*ldy + n] = acc
+    LM_EPI_RESID = 1,   // y_f32[b*ldy + n] += acc
+    LM_EPI_SWIGLU = 2,  // W = the 16-row interleaved gate|up matrix [N][K]: y_act[b*ldy + j] = act(silu(g_j) * u_j), j < N/2
+};
+// y[B][N] = x[B][K] . W[N][K]^T: x, W 16-bit of type t (W dense, ld K), f32 accumulate, B <= 8, K % 8 == 0, ldx % 8 == 0.
+// Every weight byte is read once for all B rows; fixed reduction order (bit-identical between runs).
+void launch_lm_skinny(ActType t, const uint16_t* x, int ldx, int B, const uint16_t* W, int N, int K, int epi,
+                      float* y_f32, uint16_t* y_act, int ldy, hipStream_t s);
+// launch_embed_rows for a 16-bit table (fmt 0 bf16, 1 fp16) with the ids (device values nobody validated) clamped
+// into [0, vocab)
+void launch_lm_embed(const void* table, int fmt, const int32_t* ids, int n, int vocab, int H, float* out, hipStream_t s);
+// KV cache of one layer: k_cache / v_cache [B][hkv][capacity][128] fp16, key_mask [B][capacity] int32 (shared by the
+// layers).  qkv: the fused projection's f32 rows [.][ld] = [q heads | k heads | v heads]; rope_cos / rope_sin
+// [capacity][64].
+struct LmQkvPostArgs {
+    const float* qkv = nullptr;
+    int ld = 0;
+    int hq = 0, hkv = 0;
+    const float* q_norm = nullptr;
+    const float* k_norm = nullptr;
+    const float* rope_cos = nullptr;
+    const float* rope_sin = nullptr;
+    float eps = 1e-6f;
+    float* q_out = nullptr;  // decode: [B][hq][128] f32, normalised and rotated
+    uint16_t* k_cache = nullptr;
+    uint16_t* v_cache = nullptr;
+    int32_t* key_mask = nullptr;
+    int capacity = 0;
+    int pos = 0;                        // decode: the slot every sequence appends at
+    const int32_t* mask_new = nullptr;  // decode: [B] mask of the appended token, or null = valid
+};
+// decode: one row per sequence (qkv [B][ld]) at slot a.pos
+void launch_lm_qkv_post(const LmQkvPostArgs& a, int B, hipStream_t s);
+// prefill: rows b*n + t of qkv -> slots t < n; mask [B][n] or null; the q|k|v values of a padding row (mask 0) are
+// zeroed in place and in the cache (q_out, pos and mask_new unused)
+void launch_lm_prefill_kv(const LmQkvPostArgs& a, int B, int n, const int32_t* mask, hipStream_t s);
+struct LmAttnArgs {
+    const float* q = nullptr;  // [B][hq][128] f32
+    const uint16_t* k_cache = nullptr;
+    const uint16_t* v_cache = nullptr;
+    const int32_t* key_mask = nullptr;
+    int hkv = 0, capacity = 0;
+    int nk = 0;  // keys 0 .. nk-1 (the appended one included)
+    float scale = 0.f;
+    uint16_t* out = nullptr;  // [B][hq*128] in the act type
+    float* part = nullptr;    // lm_attn_part_floats() floats when nk > LM_SPLIT_KEYS
+    int n_split = 1;          // set by launch_lm_attention
+};
+size_t lm_attn_part_floats(int B, int hq, int nk);
+void launch_lm_attention(ActType out_t, const LmAttnArgs& a, int B, int hq, hipStream_t s);
+
 // ------------------------------------------------------------ VAE decoder (kernels/vae.hip)
 // Implicit-GEMM conv on fp16 time-major activations.  A row (m, tap) = S[m + tap*dil - pad]
 // (zero row outside [0, T_in)); W [N][taps*Cin] fp16.  up == 1: conv, (m, n) -> (u = m, co = n);

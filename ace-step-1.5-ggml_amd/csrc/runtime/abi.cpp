@@ -53,6 +53,7 @@ void ace_ggml_destroy(ace_ggml_context* ctx) {
     ctx->dit.reset();
     ctx->vae.reset();
     ctx->text.reset();
+    ctx->lm.reset();
     if (ctx->d_vae) (void)hipFree(ctx->d_vae);
     if (ctx->d_in) (void)hipFree(ctx->d_in);
     if (ctx->d_v) (void)hipFree(ctx->d_v);

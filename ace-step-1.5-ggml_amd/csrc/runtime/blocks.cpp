@@ -45,7 +45,7 @@ float* BlockRunner::x(int64_t rows, int H) {
 }
 
 void BlockRunner::run(const BlockShape& sh, const std::vector<DevLayer>& layers, int n_layers, ActType at, int B,
-                      int n, const int32_t* key_mask, bool causal, hipStream_t s) {
+                      int n, const int32_t* key_mask, bool causal, hipStream_t s, const AfterQkv* after_qkv) {
     const int H = sh.hidden, D = sh.head_dim, I = sh.intermediate;
     ACEMI_CHECK(B >= 1 && n >= 1 && D == 128, "blocks: bad shape");
     ACEMI_CHECK(n_layers >= 0 && n_layers <= (int)layers.size(), "blocks: layer count");
@@ -97,6 +97,7 @@ void BlockRunner::run(const BlockShape& sh, const std::vector<DevLayer>& layers,
         const DevLayer& ly = layers[li];
         launch_rmsnorm_mod(at, x, M, H, ly.self_norm, nullptr, nullptr, 0, n, sh.eps, act, s);
         launch_gemm(act, H, ly.w_qkv.view(), M, qd + 2 * kd, H, epi_store_f32(qkv, qd + 2 * kd), s);
+        if (after_qkv) (*after_qkv)(li, qkv, qd + 2 * kd);
         launch_attn_prep(self_prep(dims, planes, qkv, qd + 2 * kd, ly.sq_norm, ly.sk_norm, get<float>(cos_),
                                    get<float>(sin_), qh, kh, vt),
                          s);

@@ -8,6 +8,7 @@
 // engine's buffers (or its cross-attention cache).
 #pragma once
 
+#include <functional>
 #include <vector>
 
 #include "../kernels.h"
@@ -31,8 +32,12 @@ class BlockRunner {
     float* x(int64_t rows, int H);
     // layers [0, n_layers) over x = [B][n][H] in place; key_mask [B][n] int32 (device) or null;
     // causal: key k > query q masked (the text encoder, qwen_model.cpp:618-637)
+    // after_qkv (optional): called for layer li once its fused QKV projection is enqueued, with the f32 rows
+    // qkv [B*n][ld] = [q | k | v] before the per-head norm and RoPE; what it enqueues on s runs before the
+    // layer's attention prep (the causal LM's prefill fills its KV cache from here, runtime/lm.cpp)
+    using AfterQkv = std::function<void(int li, float* qkv, int ld)>;
     void run(const BlockShape& sh, const std::vector<DevLayer>& layers, int n_layers, ActType act, int B, int n,
-             const int32_t* key_mask, bool causal, hipStream_t s);
+             const int32_t* key_mask, bool causal, hipStream_t s, const AfterQkv* after_qkv = nullptr);
     // out = RMSNorm(x) * w (w null: a plain copy) for all B*n rows, or each item's token 0 when first_only
     void finish(const BlockShape& sh, const float* w, int B, int n, bool first_only, float* out, hipStream_t s);
 

@@ -22,6 +22,9 @@ struct ace_ggml_context {
     std::unique_ptr<acemi::DitEngine> dit;
     std::unique_ptr<acemi::VaeEngine> vae;
     std::unique_ptr<acemi::TextEncoderEngine> text;  // ace_ggml_load_text_encoder / ace_ggml_load_lm
+    // ace_mi_load_lm: the causal LM with its KV cache (acemi::LmEngine, runtime/lm.cpp).  Type-erased so that only
+    // lm.cpp, which holds the ace_mi_lm_* entries, refers to the engine and its decode kernels.
+    std::shared_ptr<void> lm;
     void* d_vae = nullptr;  // host-ABI staging for ace_ggml_vae_decode
     size_t d_vae_bytes = 0;
     // host-ABI staging (device)

@@ -1,0 +1,331 @@
+// The 5 Hz audio-code language model on the engine: a HF Qwen3ForCausalLM with a KV cache (include/acestep_mi355x.h,
+// ace_mi_load_lm / ace_mi_lm_*), driven like the reference's `pt` backend drives transformers
+// (acestep/llm_inference.py:345-367): one prefill, then single-token steps.
+//
+//   prefill (n > 1, empty cache)  the text encoder's path: BlockRunner (MFMA GEMMs, causal flash attention, key mask);
+//                                 its after-QKV hook stores every layer's post-norm, post-RoPE K and V into the cache.
+//   decode step (n == 1)          kernels/lm_decode.hip: skinny products over the same fused matrices DevLayer holds,
+//                                 QKV post-processing, decode attention over the cache.
+// Rounding points follow BlockRunner::run: the residual stream stays f32, the input of every linear is rounded to
+// the weights' 16-bit type, products accumulate in f32.  The one deviation: prefill attention reads Q, K, V as fp16
+// hi + lo pairs (~22 bits), the decode step keeps Q in f32 and reads K and V from the cache as single fp16 values.
+//
+// This file holds both the engine and its C entries, so no other translation unit refers to the launch_lm_* kernels.
+#include <cmath>
+#include <vector>
+
+#include "context.h"
+#include "safetensors.h"
+
+namespace acemi {
+
+namespace {
+
+struct DevBuf {
+    void* p = nullptr;
+    size_t bytes = 0;
+    void ensure(size_t need) {
+        if (need == 0) need = 16;
+        if (bytes >= need) return;
+        release();
+        ACEMI_HIP(hipMalloc(&p, need));
+        bytes = need;
+    }
+    void release() {
+        if (!p) return;
+        (void)hipDeviceSynchronize();  // in-flight work may still use the buffer
+        (void)hipFree(p);
+        p = nullptr;
+        bytes = 0;
+    }
+    template <typename T>
+    T* as() const {
+        return static_cast<T*>(p);
+    }
+};
+
+}  // namespace
+
+class LmEngine {
+   public:
+    ~LmEngine() {
+        for (DevBuf* b : {&kc_, &vc_, &kmask_, &cos_, &sin_, &x_, &act_, &act2_, &qkv_, &q_, &attn_, &part_, &xn_, &xh_})
+            b->release();
+    }
+    TextModel& model() { return model_; }
+    int batch() const { return batch_; }
+    int capacity() const { return capacity_; }
+    int len() const { return len_; }
+    size_t cache_bytes() const { return kc_.bytes + vc_.bytes + kmask_.bytes; }
+    void reset() { len_ = 0; }
+
+    // bytes per position and sequence: K and V, fp16, every layer
+    size_t token_bytes() const {
+        const TextConfig& c = model_.cfg;
+        return (size_t)c.layers * 2 * c.hkv * c.head_dim * 2;
+    }
+
+    void check_weights() const {
+        for (const DevLayer& ly : model_.layers)
+            for (const DevWeight* w : {&ly.w_qkv, &ly.w_o, &ly.w_gu, &ly.w_down})
+                if (w->fmt != WF_BF16 && w->fmt != WF_F16) throw Unsupported("LM weights must be dense BF16 / F16");
+        if (!model_.head || model_.embed_fmt == 2) throw Unsupported("LM head / embed table must be 16-bit");
+    }
+
+    void begin(int B, int cap) {
+        const TextConfig& c = model_.cfg;
+        ACEMI_HIP(hipDeviceSynchronize());  // nothing in flight reads the buffers that may move
+        const size_t plane = (size_t)c.layers * B * c.hkv * cap * c.head_dim * 2;
+        kc_.ensure(plane);
+        vc_.ensure(plane);
+        kmask_.ensure((size_t)B * cap * 4);
+        if (cap > rope_n_) {  // positions 0..cap-1, ggml's recurrence (BlockRunner::run builds the same values)
+            const int half = c.head_dim / 2;
+            const float theta_scale = powf(c.rope_theta, -2.0f / (float)c.head_dim);
+            std::vector<float> cs((size_t)cap * half), sn((size_t)cap * half);
+            for (int p = 0; p < cap; ++p) {
+                float theta = (float)p;
+                for (int i = 0; i < half; ++i) {
+                    cs[(size_t)p * half + i] = (float)std::cos((double)theta);
+                    sn[(size_t)p * half + i] = (float)std::sin((double)theta);
+                    theta *= theta_scale;
+                }
+            }
+            cos_.ensure(cs.size() * 4);
+            sin_.ensure(sn.size() * 4);
+            ACEMI_HIP(hipMemcpy(cos_.p, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
+            ACEMI_HIP(hipMemcpy(sin_.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+            rope_n_ = cap;
+        }
+        const int H = c.hidden, qd = c.hq * c.head_dim, kd = c.hkv * c.head_dim, I = c.intermediate;
+        x_.ensure((size_t)LM_MAX_BATCH * H * 4);
+        act_.ensure((size_t)LM_MAX_BATCH * std::max(H, qd) * 2);
+        act2_.ensure((size_t)LM_MAX_BATCH * I * 2);
+        qkv_.ensure((size_t)LM_MAX_BATCH * (qd + 2 * kd) * 4);
+        q_.ensure((size_t)LM_MAX_BATCH * qd * 4);
+        attn_.ensure((size_t)LM_MAX_BATCH * qd * 2);
+        xn_.ensure((size_t)LM_MAX_BATCH * H * 4);
+        xh_.ensure((size_t)LM_MAX_BATCH * H * 2);
+        part_.ensure(lm_attn_part_floats(B, c.hq, cap) * 4);
+        ACEMI_HIP(hipDeviceSynchronize());  // null-stream copies: done before any stream reads them
+        batch_ = B;
+        capacity_ = cap;
+        len_ = 0;
+    }
+
+    // the caller has checked batch, capacity and the prefill rule
+    void forward(const int32_t* d_ids, const int32_t* d_mask, int n, float* d_logits, hipStream_t s) {
+        if (n > 1)
+            prefill(d_ids, d_mask, n, d_logits, s);
+        else
+            step(d_ids, d_mask, d_logits, s);
+        len_ += n;
+    }
+
+   private:
+    LmQkvPostArgs post_args(int li, const float* qkv, int ld) {
+        const TextConfig& c = model_.cfg;
+        const DevLayer& ly = model_.layers[li];
+        const size_t layer = (size_t)batch_ * c.hkv * capacity_ * c.head_dim;
+        LmQkvPostArgs a;
+        a.qkv = qkv;
+        a.ld = ld;
+        a.hq = c.hq;
+        a.hkv = c.hkv;
+        a.q_norm = ly.sq_norm;
+        a.k_norm = ly.sk_norm;
+        a.rope_cos = cos_.as<float>();
+        a.rope_sin = sin_.as<float>();
+        a.eps = c.eps;
+        a.q_out = q_.as<float>();
+        a.k_cache = kc_.as<uint16_t>() + (size_t)li * layer;
+        a.v_cache = vc_.as<uint16_t>() + (size_t)li * layer;
+        a.key_mask = kmask_.as<int32_t>();
+        a.capacity = capacity_;
+        return a;
+    }
+
+    void head(const float* x_last, int64_t row_step, float* d_logits, hipStream_t s) {
+        const TextConfig& c = model_.cfg;
+        const ActType ht = model_.head_fmt == 1 ? ActType::F16 : ActType::BF16;
+        launch_rmsnorm_f32(x_last, batch_, row_step, c.hidden, model_.norm, c.eps, xn_.as<float>(), s);
+        launch_to_act(ht, xn_.as<float>(), (int64_t)batch_ * c.hidden, false, xh_.as<uint16_t>(), s);
+        launch_lm_skinny(ht, xh_.as<uint16_t>(), c.hidden, batch_, static_cast<const uint16_t*>(model_.head), c.vocab,
+                         c.hidden, LM_EPI_STORE, d_logits, nullptr, c.vocab, s);
+    }
+
+    BlockShape shape() const {
+        const TextConfig& c = model_.cfg;
+        BlockShape sh;
+        sh.hidden = c.hidden;
+        sh.hq = c.hq;
+        sh.hkv = c.hkv;
+        sh.head_dim = c.head_dim;
+        sh.intermediate = c.intermediate;
+        sh.eps = c.eps;
+        sh.rope_theta = c.rope_theta;
+        return sh;
+    }
+
+    void prefill(const int32_t* d_ids, const int32_t* d_mask, int n, float* d_logits, hipStream_t s) {
+        const TextConfig& c = model_.cfg;
+        const BlockShape sh = shape();
+        const int M = batch_ * n;
+        float* x = blocks_.x(M, sh.hidden);
+        launch_lm_embed(model_.embed, model_.embed_fmt, d_ids, M, c.vocab, sh.hidden, x, s);
+        const BlockRunner::AfterQkv fill = [&](int li, float* qkv, int ld) {
+            launch_lm_prefill_kv(post_args(li, qkv, ld), batch_, n, d_mask, s);
+        };
+        blocks_.run(sh, model_.layers, c.layers, model_.act, batch_, n, d_mask, true, s, &fill);
+        head(x + (size_t)(n - 1) * sh.hidden, n, d_logits, s);
+    }
+
+    void step(const int32_t* d_ids, const int32_t* d_mask, float* d_logits, hipStream_t s) {
+        const TextConfig& c = model_.cfg;
+        const int B = batch_, H = c.hidden, D = c.head_dim, qd = c.hq * D, kd = c.hkv * D, I = c.intermediate;
+        const ActType at = model_.act;
+        float* x = x_.as<float>();
+        uint16_t* act = act_.as<uint16_t>();
+        uint16_t* act2 = act2_.as<uint16_t>();
+        uint16_t* attn = attn_.as<uint16_t>();
+        float* qkv = qkv_.as<float>();
+        launch_lm_embed(model_.embed, model_.embed_fmt, d_ids, B, c.vocab, H, x, s);
+        for (int li = 0; li < c.layers; ++li) {
+            const DevLayer& ly = model_.layers[li];
+            launch_rmsnorm_mod(at, x, B, H, ly.self_norm, nullptr, nullptr, 0, 1, c.eps, act, s);
+            launch_lm_skinny(at, act, H, B, static_cast<const uint16_t*>(ly.w_qkv.q), qd + 2 * kd, H, LM_EPI_STORE, qkv,
+                             nullptr, qd + 2 * kd, s);
+            LmQkvPostArgs pa = post_args(li, qkv, qd + 2 * kd);
+            pa.pos = len_;
+            pa.mask_new = d_mask;
+            launch_lm_qkv_post(pa, B, s);
+            LmAttnArgs aa;
+            aa.q = q_.as<float>();
+            aa.k_cache = pa.k_cache;
+            aa.v_cache = pa.v_cache;
+            aa.key_mask = pa.key_mask;
+            aa.hkv = c.hkv;
+            aa.capacity = capacity_;
+            aa.nk = len_ + 1;
+            aa.scale = 1.0f / std::sqrt((float)D);
+            aa.out = attn;
+            aa.part = part_.as<float>();
+            launch_lm_attention(at, aa, B, c.hq, s);
+            launch_lm_skinny(at, attn, qd, B, static_cast<const uint16_t*>(ly.w_o.q), H, qd, LM_EPI_RESID, x, nullptr, H, s);
+            launch_rmsnorm_mod(at, x, B, H, ly.mlp_norm, nullptr, nullptr, 0, 1, c.eps, act, s);
+            launch_lm_skinny(at, act, H, B, static_cast<const uint16_t*>(ly.w_gu.q), 2 * I, H, LM_EPI_SWIGLU, nullptr, act2,
+                             I, s);
+            launch_lm_skinny(at, act2, I, B, static_cast<const uint16_t*>(ly.w_down.q), H, I, LM_EPI_RESID, x, nullptr, H, s);
+        }
+        head(x, 1, d_logits, s);
+    }
+
+    TextModel model_;
+    BlockRunner blocks_;
+    DevBuf kc_, vc_, kmask_, cos_, sin_, x_, act_, act2_, qkv_, q_, attn_, part_, xn_, xh_;
+    int batch_ = 0, capacity_ = 0, len_ = 0, rope_n_ = 0;
+};
+
+}  // namespace acemi
+
+using namespace acemi_abi;
+
+namespace {
+acemi::LmEngine* lm_of(ace_ggml_context* ctx) { return static_cast<acemi::LmEngine*>(ctx->lm.get()); }
+}  // namespace
+
+extern "C" {
+
+ace_ggml_status ace_mi_load_lm(ace_ggml_context* ctx, const char* model_dir) {
+    if (!ctx || !model_dir) return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        bind_device(ctx);
+        ACEMI_HIP(hipStreamSynchronize(ctx->stream));
+        ctx->lm.reset();  // the previous LM and its cache
+        auto eng = std::make_shared<acemi::LmEngine>();
+        acemi::TextLoadOptions opt;
+        opt.model_prefix = true;
+        opt.lm_head = true;
+        opt.dense16_only = true;
+        acemi::load_text_model(model_dir, eng->model(), opt);
+        eng->check_weights();
+        ctx->lm = std::move(eng);
+    } catch (const acemi::HipError& e) {
+        return set_error(ctx, ACE_GGML_ERR, e.what());
+    } catch (const acemi::Unsupported& e) {
+        return set_error(ctx, ACE_GGML_ERR_UNSUPPORTED, e.what());
+    } catch (const std::exception& e) {
+        return set_error(ctx, ACE_GGML_ERR_IO, e.what());
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_lm_get_info(ace_ggml_context* ctx, ace_mi_lm_info* out) {
+    if (!ctx || !out) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->lm) return set_error(ctx, ACE_GGML_ERR, "lm not loaded");
+    acemi::LmEngine* e = lm_of(ctx);
+    const acemi::TextConfig& c = e->model().cfg;
+    out->vocab_size = c.vocab;
+    out->hidden_size = c.hidden;
+    out->num_layers = c.layers;
+    out->num_heads = c.hq;
+    out->num_kv_heads = c.hkv;
+    out->head_dim = c.head_dim;
+    out->max_positions = c.max_pos;
+    out->tied = e->model().tied ? 1 : 0;
+    out->act_type = e->model().act == acemi::ActType::F16 ? 1 : 0;
+    out->batch = e->batch();
+    out->capacity = e->capacity();
+    out->cache_len = e->len();
+    out->weight_bytes = (int64_t)e->model().weight_bytes;
+    out->cache_bytes = (int64_t)e->cache_bytes();
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_lm_begin(ace_ggml_context* ctx, int32_t batch, int32_t capacity) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->lm) return set_error(ctx, ACE_GGML_ERR, "lm not loaded");
+    acemi::LmEngine* e = lm_of(ctx);
+    if (batch < 1 || batch > acemi::LM_MAX_BATCH)
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm batch must be 1..8");
+    if (capacity < 1 || capacity > e->model().cfg.max_pos)
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm capacity must be 1..max_position_embeddings");
+    try {
+        bind_device(ctx);
+        e->begin(batch, capacity);
+    } catch (const std::exception& ex) {
+        return set_error(ctx, ACE_GGML_ERR, std::string("lm begin failed: ") + ex.what());
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_lm_forward(ace_ggml_context* ctx, const int32_t* d_ids, const int32_t* d_mask, int32_t n,
+                                  float* d_logits, void* stream) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->lm) return set_error(ctx, ACE_GGML_ERR, "lm not loaded");
+    if (!d_ids || !d_logits || n <= 0) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm forward: null pointer or n <= 0");
+    acemi::LmEngine* e = lm_of(ctx);
+    if (e->batch() <= 0) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm forward: ace_mi_lm_begin was not called");
+    if ((int64_t)e->len() + n > e->capacity())
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm forward: exceeds the cache capacity");
+    if (n > 1 && e->len() > 0)
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm forward: a prefill (n > 1) needs an empty cache");
+    try {
+        bind_device(ctx);
+        acemi::gemm_splitk_check();
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+        e->forward(d_ids, d_mask, n, d_logits, s);
+    } catch (const std::exception& ex) {
+        return set_error(ctx, ACE_GGML_ERR, std::string("lm forward failed: ") + ex.what());
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_lm_reset(ace_ggml_context* ctx) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->lm) return set_error(ctx, ACE_GGML_ERR, "lm not loaded");
+    lm_of(ctx)->reset();
+    return ACE_GGML_OK;
+}
+
+}  // extern "C"

@@ -42,6 +42,8 @@ void load_text_config(const std::string& path, TextConfig& c) {  // qwen_config.
         c.eps = (float)o.at("rms_norm_eps").as_num();
         if (o.has("rope_theta")) c.rope_theta = (float)o.at("rope_theta").as_num();
         if (o.has("dtype") && o.at("dtype").kind == Json::String) c.dtype = o.at("dtype").as_str();
+        if (o.has("tie_word_embeddings") && o.at("tie_word_embeddings").kind == Json::Bool)
+            c.tie_word_embeddings = o.at("tie_word_embeddings").b ? 1 : 0;
     } catch (const IoError&) {
         throw;
     } catch (const std::exception& e) {
@@ -64,11 +66,16 @@ std::string resolve_text_gguf(const std::string& dir) {
 
 }  // namespace
 
-void load_text_model(const std::string& dir, TextModel& m) {
+void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions& opt) {
     namespace fs = std::filesystem;
     const fs::path p(dir);
     const fs::path root = p.extension() == ".gguf" ? p.parent_path() : p;
     const std::string gguf_path = resolve_text_gguf(dir);
+    if (opt.dense16_only) {
+        if (!gguf_path.empty()) throw Unsupported("quantized LM weights are not supported: GGUF checkpoint " + gguf_path);
+        if (quant::from_env("ACE_GGML_QWEN_WEIGHT_QTYPE") != quant::QNONE)
+            throw Unsupported("quantized LM weights are not supported: unset ACE_GGML_QWEN_WEIGHT_QTYPE (16-bit BF16 / F16 only)");
+    }
     TextConfig& c = m.cfg;
     load_text_config((root / "config.json").string(), c);
     if (c.head_dim != 128) throw Unsupported("text encoder head_dim must be 128");
@@ -89,6 +96,13 @@ void load_text_model(const std::string& dir, TextModel& m) {
         L.gg.open(gguf_path);
     } else {
         L.st.open((root / "model.safetensors").string());
+        if (opt.model_prefix) {  // HF Qwen3ForCausalLM names: "model.layers.0...." beside "lm_head.weight"
+            std::vector<std::pair<std::string, StTensor>> bare;
+            for (const auto& kv : L.st.tensors)
+                if (kv.first.rfind("model.", 0) == 0 && !L.st.has(kv.first.substr(6)))
+                    bare.emplace_back(kv.first.substr(6), kv.second);
+            for (auto& kv : bare) L.st.tensors[kv.first] = kv.second;
+        }
     }
     const int H = c.hidden, I = c.intermediate, D = c.head_dim, qd = c.hq * D, kd = c.hkv * D;
     {  // embed_tokens: ggml_get_rows + cast_f32 yields the stored values (dequantized if quantized)
@@ -99,6 +113,8 @@ void load_text_model(const std::string& dir, TextModel& m) {
                 m.embed = L.upload<uint16_t>(e.u16.data(), e.u16.size() * 2);
             }
         }
+        if (!m.embed && opt.dense16_only)
+            throw Unsupported("LM embed_tokens.weight has dtype " + e.dtype + " (16-bit BF16 / F16 only)");
         if (!m.embed) {
             std::vector<float> v = L.values(e);
             if (e.dtype != "Q" && quant::applies(L.qt, H)) {  // quantized at load, read back by get_rows
@@ -127,6 +143,22 @@ void load_text_model(const std::string& dir, TextModel& m) {
         ly.w_o = L.finish(L.mat(p2 + "self_attn.o_proj.weight", H, qd));
         ly.w_gu = L.gate_up(p2, I, H);
         ly.w_down = L.finish(L.mat(p2 + "mlp.down_proj.weight", H, I));
+    }
+    if (opt.lm_head) {
+        if (L.has("lm_head.weight")) {
+            const Mat hw = L.mat("lm_head.weight", c.vocab, H);
+            if (hw.dtype != "BF16" && hw.dtype != "F16")
+                throw Unsupported("LM lm_head.weight has dtype " + hw.dtype + " (16-bit BF16 / F16 only)");
+            m.head_fmt = hw.dtype == "BF16" ? 0 : 1;
+            m.head = L.upload<uint16_t>(hw.u16.data(), hw.u16.size() * 2);
+        } else if (c.tie_word_embeddings == 0) {
+            throw IoError("missing tensor: lm_head.weight (tie_word_embeddings is false)");
+        } else {
+            if (m.embed_fmt == 2) throw Unsupported("a tied LM head needs a 16-bit embed_tokens.weight");
+            m.head = m.embed;
+            m.head_fmt = m.embed_fmt;
+            m.tied = true;
+        }
     }
     m.act = m.layers.empty() ? ActType::BF16 : m.layers[0].w_qkv.act();
     for (const DevLayer& ly : m.layers)

@@ -16,6 +16,7 @@ struct TextConfig {
     int vocab = 0, hidden = 0, layers = 0, hq = 0, hkv = 0, intermediate = 0, head_dim = 0, max_pos = 0;
     float eps = 1e-6f, rope_theta = 1000000.0f;
     std::string dtype;
+    int tie_word_embeddings = -1;  // config.json tie_word_embeddings: -1 absent, 0 false, 1 true
 };
 
 struct TextModel {
@@ -26,13 +27,25 @@ struct TextModel {
     std::vector<DevLayer> layers;
     ActType act = ActType::BF16;
     int qtype = 0;
+    // causal-LM head (TextLoadOptions::lm_head): [vocab][hidden] 16-bit, lm_head.weight or the tied embed table
+    void* head = nullptr;
+    int head_fmt = 0;  // 0 bf16, 1 fp16
+    bool tied = false;
     std::vector<void*> allocs;
     size_t weight_bytes = 0;
     ~TextModel();
 };
 
+// What ace_mi_load_lm asks of the loader beyond the text encoder's behaviour (all off = ace_ggml_load_text_encoder /
+// ace_ggml_load_lm exactly as before).
+struct TextLoadOptions {
+    bool model_prefix = false;   // also accept the HF causal-LM names "model.<tensor>"
+    bool lm_head = false;        // resolve the head: lm_head.weight when the file has it, else the tied embed table
+    bool dense16_only = false;   // refuse GGUF files, ACE_GGML_QWEN_WEIGHT_QTYPE and a non-16-bit embed table (Unsupported)
+};
+
 // Throws std::runtime_error (the ABI reports ACE_GGML_ERR_IO like load_qwen_dir, acestep_ggml.cpp:238-244).
-void load_text_model(const std::string& dir, TextModel& m);
+void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions& opt = TextLoadOptions());
 
 class TextEncoderEngine {
    public:

@@ -209,6 +209,49 @@ ACE_GGML_API ace_ggml_status ace_mi_build_condition(ace_ggml_context* ctx, const
                                                     int32_t refer_len, float* out_enc, size_t out_enc_size,
                                                     int32_t* out_mask, size_t out_mask_size, int32_t* out_len);
 
+/* ---- the 5 Hz audio-code language model (acestep/llm_inference.py): a HF Qwen3ForCausalLM with a KV cache, driven
+ * the way the reference's `pt` backend drives transformers: one prefill `model(input_ids, attention_mask,
+ * use_cache=True)`, then single-token calls with `past_key_values` (llm_inference.py:345-367).  The engine supplies
+ * the last position's logits; the constrained-decoding FSM, CFG mixing and sampling stay with the caller.
+ * d_* are device pointers and the forward is stream-ordered like ace_mi_dit_forward_batched. ---- */
+typedef struct ace_mi_lm_info {
+    int32_t vocab_size;
+    int32_t hidden_size;
+    int32_t num_layers;
+    int32_t num_heads;
+    int32_t num_kv_heads;
+    int32_t head_dim;
+    int32_t max_positions;   /* max_position_embeddings */
+    int32_t tied;            /* 1: the head is the embed_tokens table */
+    int32_t act_type;        /* 0 = bf16, 1 = fp16 */
+    int32_t batch;           /* of the last ace_mi_lm_begin (0 before it) */
+    int32_t capacity;
+    int32_t cache_len;       /* positions held per sequence */
+    int64_t weight_bytes;
+    int64_t cache_bytes;     /* device memory of the KV cache */
+} ace_mi_lm_info;
+/* Load a HF Qwen3ForCausalLM directory (config.json + model.safetensors, tensor names with or without the "model."
+ * prefix; lm_head.weight when present, else the tied embed_tokens.weight, honouring tie_word_embeddings) into a slot
+ * of its own: the text encoder of ace_ggml_load_text_encoder / ace_ggml_load_lm stays resident beside it.  16-bit
+ * checkpoints only: ACE_GGML_QWEN_WEIGHT_QTYPE, a GGUF file or an F32 embed table are ACE_GGML_ERR_UNSUPPORTED.
+ * Frees the KV cache of a previous LM. */
+ACE_GGML_API ace_ggml_status ace_mi_load_lm(ace_ggml_context* ctx, const char* model_dir);
+ACE_GGML_API ace_ggml_status ace_mi_lm_get_info(ace_ggml_context* ctx, ace_mi_lm_info* out);
+/* Allocate (or reuse, when it fits) and reset the KV cache for `batch` sequences (1..8) of up to `capacity`
+ * positions (1..max_positions); ACE_GGML_ERR_INVALID_ARG otherwise.  Synchronous. */
+ACE_GGML_API ace_ggml_status ace_mi_lm_begin(ace_ggml_context* ctx, int32_t batch, int32_t capacity);
+/* Append n tokens per sequence at positions len .. len+n-1 (slot indices, padding included, as transformers does
+ * without position_ids) and write the logits of the last appended position: d_ids [batch][n] int32, d_mask [batch][n]
+ * int32 or NULL (0 = a padding key no query ever attends to; remembered), d_logits [batch][vocab] f32.  n > 1 is the
+ * prefill, allowed on an empty cache only (MFMA GEMMs + causal flash attention); n == 1 is the decode step
+ * (kernels/lm_decode.hip), also on an empty cache.  Token ids outside [0, vocab) are clamped into it.
+ * ACE_GGML_ERR_INVALID_ARG, with the cache unchanged, when len + n exceeds the capacity or n > 1 on a non-empty
+ * cache; ACE_GGML_ERR "lm not loaded" before ace_mi_load_lm. */
+ACE_GGML_API ace_ggml_status ace_mi_lm_forward(ace_ggml_context* ctx, const int32_t* d_ids, const int32_t* d_mask,
+                                               int32_t n, float* d_logits, void* stream);
+/* Cache length back to 0 (batch and capacity kept). */
+ACE_GGML_API ace_ggml_status ace_mi_lm_reset(ace_ggml_context* ctx);
+
 /* The x_T stream of the reference generator (std::mt19937(seed) + std::normal_distribution<float>,
  * acestep_ggml.cpp:2043-2048) as the generate entries draw it: n values into out (host). */
 ACE_GGML_API ace_ggml_status ace_mi_reference_noise(int32_t seed, int64_t n, float* out);

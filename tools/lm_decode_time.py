@@ -1,0 +1,161 @@
+#!/usr/bin/env python
+"""ms per decode step of the engine's causal LM (ace_mi_lm_forward, n = 1) with synthetic weights at the Qwen3-0.6B and
+Qwen3-1.7B shapes (the models' public config.json), beside two numbers from the same run:
+
+  * the bytes a step must read (every layer's matrices and the head once, plus the KV cache of B sequences) divided by
+    the HBM bandwidth (8.0 TB/s peak, 6.3 TB/s measured achievable);
+  * the per-token time of transformers' Qwen3ForCausalLM in torch eager (bf16) on the same GPU with the same weights,
+    called as the reference's _forward_pass calls it: model(input_ids=[B, 1], attention_mask, past_key_values,
+    use_cache=True).
+
+The 5 Hz LM extends the stock vocabulary with audio-code tokens: --vocab sets the size (default: stock Qwen3, 151936).
+Each step is timed on its own with a pair of events after warm-up steps; the table gives median, min and max.
+
+  python tools/lm_decode_time.py --models 0.6b,1.7b --steps 30 --warmup 5 [--no-torch] [--json out.json]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "ace-step-1.5-ggml_amd"))
+sys.path.insert(0, ROOT)
+
+SHAPES = {  # Qwen/Qwen3-0.6B and Qwen/Qwen3-1.7B config.json
+    "0.6b": dict(hidden_size=1024, num_hidden_layers=28, num_attention_heads=16, num_key_value_heads=8,
+                 intermediate_size=3072, head_dim=128, max_position_embeddings=40960, rms_norm_eps=1e-6,
+                 rope_theta=1000000.0),
+    "1.7b": dict(hidden_size=2048, num_hidden_layers=28, num_attention_heads=16, num_key_value_heads=8,
+                 intermediate_size=6144, head_dim=128, max_position_embeddings=40960, rms_norm_eps=1e-6,
+                 rope_theta=1000000.0),
+}
+HBM_PEAK, HBM_MEASURED = 8.0e12, 6.3e12
+
+
+def step_bytes(cfg, B, cache_len):
+    H, I, D = cfg["hidden_size"], cfg["intermediate_size"], cfg["head_dim"]
+    qd, kd = cfg["num_attention_heads"] * D, cfg["num_key_value_heads"] * D
+    layer = ((qd + 2 * kd) * H + H * qd + 2 * I * H + H * I) * 2
+    weights = cfg["num_hidden_layers"] * layer + cfg["vocab_size"] * H * 2
+    cache = B * cache_len * cfg["num_hidden_layers"] * 2 * kd * 2          # K and V, fp16
+    return weights, cache
+
+
+def time_steps(step, n_warm, n_steps):
+    import torch
+    for _ in range(n_warm):
+        step()
+    ms = []
+    for _ in range(n_steps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        step()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return dict(median=statistics.median(ms), min=min(ms), max=max(ms))
+
+
+def engine_times(ckpt, cfg, Bs, lens, warm, steps):
+    import torch
+    from acestep_mi355x.capi import GGMLCAPIBridge
+    br = GGMLCAPIBridge()
+    br.load_lm(ckpt)
+    out = {}
+    g = torch.Generator().manual_seed(0)
+    for B in Bs:
+        for L in lens:
+            br.lm_begin(B, L + warm + steps)
+            ids = torch.randint(0, cfg["vocab_size"], (B, L), generator=g, dtype=torch.int32).cuda()
+            br.lm_forward(ids)
+            tok = ids[:, :1].contiguous()
+            out[(B, L)] = time_steps(lambda: br.lm_forward(tok), warm, steps)
+    br.close()
+    return out
+
+
+def torch_times(ckpt, cfg, Bs, lens, warm, steps):
+    import torch
+    from safetensors.torch import load_file
+    from transformers import Qwen3Config, Qwen3ForCausalLM
+    hf = Qwen3Config(**{k: v for k, v in cfg.items() if k not in ("architectures",)}, attention_bias=False)
+    with torch.device("cuda"):
+        model = Qwen3ForCausalLM(hf).to(torch.bfloat16).eval()
+    missing, unexpected = model.load_state_dict(load_file(os.path.join(ckpt, "model.safetensors"), device="cuda"),
+                                                strict=False)
+    assert not unexpected, unexpected
+    model.tie_weights()
+    out = {}
+    g = torch.Generator().manual_seed(0)
+    with torch.no_grad():
+        for B in Bs:
+            for L in lens:
+                ids = torch.randint(0, cfg["vocab_size"], (B, L), generator=g).cuda()
+                state = {"mask": torch.ones((B, L), dtype=torch.long, device="cuda")}
+                state["past"] = model(input_ids=ids, attention_mask=state["mask"], use_cache=True).past_key_values
+                tok = ids[:, :1].contiguous()
+
+                def step():
+                    state["mask"] = torch.cat([state["mask"], state["mask"][:, :1]], dim=1)
+                    o = model(input_ids=tok, attention_mask=state["mask"], past_key_values=state["past"], use_cache=True)
+                    state["past"] = o.past_key_values
+                    return o.logits[:, -1, :]
+                out[(B, L)] = time_steps(step, warm, steps)
+                del state
+    del model
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--models", default="0.6b,1.7b")
+    ap.add_argument("--vocab", type=int, default=151936)
+    ap.add_argument("--batch", default="1,2")
+    ap.add_argument("--cache", default="256,1024,4096")
+    ap.add_argument("--steps", type=int, default=30)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--json", default=None)
+    a = ap.parse_args()
+    Bs, lens = [int(x) for x in a.batch.split(",")], [int(x) for x in a.cache.split(",")]
+    rows = []
+    print("| model | B | cache | engine ms/step median (min-max) | bytes/step MB (weights + cache) | bytes / 8.0 TB/s ms "
+          "| bytes / 6.3 TB/s ms | torch eager ms/token median (min-max) | torch / engine |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    for name in a.models.split(","):
+        cfg = dict(SHAPES[name], vocab_size=a.vocab)
+        with tempfile.TemporaryDirectory(prefix="acemi_lmtime_") as d:
+            _write(d, cfg)
+            eng = engine_times(d, cfg, Bs, lens, a.warmup, a.steps)
+            ref = {} if a.no_torch else torch_times(d, dict(cfg, tie_word_embeddings=True), Bs, lens, a.warmup, a.steps)
+        for B in Bs:
+            for L in lens:
+                w, c = step_bytes(cfg, B, L)
+                e, t = eng[(B, L)], ref.get((B, L))
+                row = dict(model=name, B=B, cache=L, engine_ms=e, weight_bytes=w, cache_bytes=c,
+                           roofline_peak_ms=(w + c) / HBM_PEAK * 1e3, roofline_measured_ms=(w + c) / HBM_MEASURED * 1e3,
+                           torch_ms=t)
+                rows.append(row)
+                ts = f"{t['median']:.3f} ({t['min']:.3f}-{t['max']:.3f})" if t else "-"
+                ratio = f"{t['median'] / e['median']:.2f}x" if t else "-"
+                print(f"| {name} | {B} | {L} | {e['median']:.3f} ({e['min']:.3f}-{e['max']:.3f}) | "
+                      f"{(w + c) / 1e6:.0f} ({w / 1e6:.0f} + {c / 1e6:.0f}) | {row['roofline_peak_ms']:.3f} | "
+                      f"{row['roofline_measured_ms']:.3f} | {ts} | {ratio} |", flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(rows, f, indent=1)
+
+
+def _write(d, cfg):
+    """write_lm_checkpoint with the multi-threaded torch generator (hundreds of millions of values)."""
+    from acestep_mi355x.synthetic import lm_tensor_specs, write_checkpoint
+    cfg = dict(cfg, architectures=["Qwen3ForCausalLM"], tie_word_embeddings=True)
+    return write_checkpoint(d, cfg, seed=1, dtype="BF16", backend="torch", specs=lm_tensor_specs(cfg, tied=True))
+
+
+if __name__ == "__main__":
+    main()
