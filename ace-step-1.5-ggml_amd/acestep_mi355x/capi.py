@@ -51,7 +51,9 @@ SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_ben
                     "ace_mi_kernel_gemm_q", "ace_mi_kernel_dequant", "ace_mi_bench_gemm_q", "ace_mi_kernel_gemm_a8",
                     "ace_mi_kernel_gemm_a8_mode", "ace_mi_kernel_attn_kh", "ace_mi_kernel_lora_merge",
                     "ace_mi_kernel_dequant_blocks", "ace_mi_kernel_dequant_segments", "ace_mi_bench_dequant_blocks",
-                    "ace_mi_gemm_resolve", "ace_mi_gemm_variant_row", "ace_mi_gemm_variant_arg_ok")
+                    "ace_mi_gemm_resolve", "ace_mi_gemm_variant_row", "ace_mi_gemm_variant_arg_ok",
+                    "ace_mi_kernel_lm_skinny", "ace_mi_kernel_lm_embed", "ace_mi_kernel_lm_qkv_post",
+                    "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention")
 
 # qtype codes of ace_mi_quantize & co. (names as parse_quant_type, acestep_dit_model.cpp:27-37)
 QTYPES = {"q8_0": 1, "q4_k": 2, "q6_k": 3,
@@ -307,6 +309,7 @@ def load_selftest_library() -> ctypes.CDLL:
     lib.ace_mi_bench_dequant_blocks.argtypes = [i32, i32, i32, i32, i32, fp]
     lib.ace_mi_bench_dequant_blocks.restype = ctypes.c_int
     _bind_gemm_variants(lib)
+    _bind_lm_kernels(lib)
     _SELFTEST = lib
     return lib
 
@@ -916,6 +919,117 @@ def kernel_lora_merge(base_bits: Optional[np.ndarray], out_bits: np.ndarray, col
                                       arr, len(jobs))
     if st != ACE_GGML_OK:
         raise RuntimeError(f"ace_mi_kernel_lora_merge failed (status={st})")
+    return out
+
+
+LM_EPI_STORE, LM_EPI_RESID, LM_EPI_SWIGLU = 0, 1, 2
+
+
+def _bind_lm_kernels(lib):
+    i32, f32 = ctypes.c_int32, ctypes.c_float
+    fp, ip, u16p = ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint16)
+    lib.ace_mi_kernel_lm_skinny.argtypes = [i32] * 7 + [u16p, u16p, fp, u16p]
+    lib.ace_mi_kernel_lm_embed.argtypes = [i32] * 4 + [u16p, ip, fp]
+    lib.ace_mi_kernel_lm_qkv_post.argtypes = [i32] * 6 + [f32, fp, fp, fp, fp, fp, ip, fp, u16p, u16p, ip]
+    lib.ace_mi_kernel_lm_prefill_kv.argtypes = [i32] * 6 + [f32, fp, fp, fp, fp, ip, u16p, u16p, ip]
+    lib.ace_mi_kernel_lm_attention.argtypes = [i32] * 6 + [f32, fp, u16p, u16p, ip, u16p]
+    for name in ("skinny", "embed", "qkv_post", "prefill_kv", "attention"):
+        getattr(lib, "ace_mi_kernel_lm_" + name).restype = ctypes.c_int
+    return lib
+
+
+def _u16ptr(a: Optional[np.ndarray]):
+    return None if a is None else a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint16))
+
+
+def _lm_lib(lib):
+    """`lib`: a loaded library that exports the ace_mi_kernel_lm_* entries (default: the GPU self-test library)."""
+    return _bind_lm_kernels(lib) if lib is not None else load_selftest_library()
+
+
+def _lm_status(name: str, st: int):
+    if st != ACE_GGML_OK:
+        raise RuntimeError(f"ace_mi_kernel_lm_{name} failed (status={st})")
+
+
+def kernel_lm_skinny(x_bits: np.ndarray, w_bits: np.ndarray, y0: np.ndarray, epi: int = 0, act_type: int = 0,
+                     lib=None) -> np.ndarray:
+    """launch_lm_skinny on host arrays: x_bits [B][ldx] and w_bits [N][K] 16-bit words of act_type (0 bf16, 1 fp16);
+    y0 [B][ldy] = the initial content of the destination, float32 for epi 0 (store) / 1 (add), uint16 for epi 2
+    (SwiGLU on gate|up interleaved rows, N / 2 columns).  Returns the destination after the launch, padding included."""
+    lib = _lm_lib(lib)
+    x = np.ascontiguousarray(x_bits, dtype=np.uint16)
+    w = np.ascontiguousarray(w_bits, dtype=np.uint16)
+    y = np.array(y0, dtype=np.uint16 if epi == LM_EPI_SWIGLU else np.float32, order="C", copy=True)
+    st = lib.ace_mi_kernel_lm_skinny(act_type, epi, x.shape[0], w.shape[0], w.shape[1], x.shape[1], y.shape[1],
+                                     _u16ptr(x), _u16ptr(w), None if epi == LM_EPI_SWIGLU else _fptr(y),
+                                     _u16ptr(y) if epi == LM_EPI_SWIGLU else None)
+    _lm_status("skinny", st)
+    return y
+
+
+def kernel_lm_embed(table_bits: np.ndarray, ids: np.ndarray, fmt: int = 0, lib=None) -> np.ndarray:
+    """launch_lm_embed: table_bits [vocab][H] 16-bit words of fmt (0 bf16, 1 fp16), ids [n] int32 -> f32 [n][H]."""
+    lib = _lm_lib(lib)
+    t = np.ascontiguousarray(table_bits, dtype=np.uint16)
+    i = np.ascontiguousarray(ids, dtype=np.int32)
+    out = np.full((i.shape[0], t.shape[1]), np.nan, dtype=np.float32)
+    _lm_status("embed", lib.ace_mi_kernel_lm_embed(fmt, i.shape[0], t.shape[0], t.shape[1], _u16ptr(t), _iptr(i),
+                                                   _fptr(out)))
+    return out
+
+
+def kernel_lm_qkv_post(qkv: np.ndarray, hq: int, hkv: int, pos: int, eps: float, q_norm, k_norm, rope_cos, rope_sin,
+                       mask_new, k_cache: np.ndarray, v_cache: np.ndarray, key_mask: np.ndarray, lib=None):
+    """launch_lm_qkv_post: qkv [B][ld] f32, norms [128], rope tables [capacity][64], mask_new [B] int32 or None; the
+    caches [B][hkv][capacity][128] uint16 and key_mask [B][capacity] int32 hold the initial content.  Returns
+    (q_out [B][hq][128] f32, k_cache, v_cache, key_mask) after the launch."""
+    lib = _lm_lib(lib)
+    x = np.ascontiguousarray(qkv, dtype=np.float32)
+    qn, kn = (np.ascontiguousarray(a, dtype=np.float32) for a in (q_norm, k_norm))
+    cs, sn = (np.ascontiguousarray(a, dtype=np.float32) for a in (rope_cos, rope_sin))
+    mn = None if mask_new is None else np.ascontiguousarray(mask_new, dtype=np.int32)
+    kc, vc = (np.array(a, dtype=np.uint16, order="C", copy=True) for a in (k_cache, v_cache))
+    km = np.array(key_mask, dtype=np.int32, order="C", copy=True)
+    B, cap = km.shape
+    q = np.full((B, hq, 128), np.nan, dtype=np.float32)
+    st = lib.ace_mi_kernel_lm_qkv_post(B, hq, hkv, cap, pos, x.shape[1], eps, _fptr(x), _fptr(qn), _fptr(kn), _fptr(cs),
+                                       _fptr(sn), _iptr(mn), _fptr(q), _u16ptr(kc), _u16ptr(vc), _iptr(km))
+    _lm_status("qkv_post", st)
+    return q, kc, vc, km
+
+
+def kernel_lm_prefill_kv(qkv: np.ndarray, n: int, hq: int, hkv: int, eps: float, k_norm, rope_cos, rope_sin, mask,
+                         k_cache: np.ndarray, v_cache: np.ndarray, key_mask: np.ndarray, lib=None):
+    """launch_lm_prefill_kv: qkv [B * n][ld] f32 (rows b * n + t), mask [B][n] int32 or None; caches and key_mask as
+    kernel_lm_qkv_post.  Returns (qkv, k_cache, v_cache, key_mask) after the launch."""
+    lib = _lm_lib(lib)
+    x = np.array(qkv, dtype=np.float32, order="C", copy=True)
+    kn = np.ascontiguousarray(k_norm, dtype=np.float32)
+    cs, sn = (np.ascontiguousarray(a, dtype=np.float32) for a in (rope_cos, rope_sin))
+    m = None if mask is None else np.ascontiguousarray(mask, dtype=np.int32)
+    kc, vc = (np.array(a, dtype=np.uint16, order="C", copy=True) for a in (k_cache, v_cache))
+    km = np.array(key_mask, dtype=np.int32, order="C", copy=True)
+    B, cap = km.shape
+    st = lib.ace_mi_kernel_lm_prefill_kv(B, hq, hkv, cap, n, x.shape[1], eps, _fptr(x), _fptr(kn), _fptr(cs), _fptr(sn),
+                                         _iptr(m), _u16ptr(kc), _u16ptr(vc), _iptr(km))
+    _lm_status("prefill_kv", st)
+    return x, kc, vc, km
+
+
+def kernel_lm_attention(q: np.ndarray, k_cache: np.ndarray, v_cache: np.ndarray, key_mask: np.ndarray, nk: int,
+                        scale: float, out_type: int = 0, lib=None) -> np.ndarray:
+    """launch_lm_attention over keys 0 .. nk-1: q [B][hq][128] f32, caches [B][hkv][capacity][128] uint16 (fp16 words),
+    key_mask [B][capacity] int32 -> uint16 [B][hq][128] words of out_type (0 bf16, 1 fp16)."""
+    lib = _lm_lib(lib)
+    qq = np.ascontiguousarray(q, dtype=np.float32)
+    kc, vc = (np.ascontiguousarray(a, dtype=np.uint16) for a in (k_cache, v_cache))
+    km = np.ascontiguousarray(key_mask, dtype=np.int32)
+    B, hq = qq.shape[0], qq.shape[1]
+    out = np.full((B, hq, 128), 0x7fff, dtype=np.uint16)
+    st = lib.ace_mi_kernel_lm_attention(out_type, B, hq, kc.shape[1], kc.shape[2], nk, scale, _fptr(qq), _u16ptr(kc),
+                                        _u16ptr(vc), _iptr(km), _u16ptr(out))
+    _lm_status("attention", st)
     return out
 
 

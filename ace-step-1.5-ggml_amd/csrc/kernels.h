@@ -405,6 +405,8 @@ struct LmAttnArgs {
     int n_split = 1;          // set by launch_lm_attention
 };
 size_t lm_attn_part_floats(int B, int hq, int nk);
+// out = softmax(scale q.k over the keys with key_mask != 0) . V; a masked key's K and V never reach the result, slots
+// >= nk are not read, and a sequence whose keys are all masked gets exactly +0 in every output word of either type.
 void launch_lm_attention(ActType out_t, const LmAttnArgs& a, int B, int hq, hipStream_t s);
 
 // ------------------------------------------------------------ VAE decoder (kernels/vae.hip)

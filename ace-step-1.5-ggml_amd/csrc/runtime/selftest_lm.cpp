@@ -1,0 +1,207 @@
+// Kernel self-test entries of the LM decode kernels (kernels/lm_decode.hip; include/acestep_mi355x_selftest.h): one
+// launch_lm_* call on host buffers, blocking, so that tests/lm_kernel_cases.py can compare each kernel with a float64
+// reference of the same operation.  Built into libacestep_mi355x_selftest.so (Makefile target `selftest`) and, on top
+// of tests/host/lm_emul.cpp, into the LM host library (tests/lmhostlib.py); not part of runtime/selftest.cpp, which the
+// host library of tests/hostlib.py compiles without the LM kernels.
+#include <cstdio>
+#include <cstring>
+
+#include "../../../include/acestep_mi355x_selftest.h"
+#include "../kernels.h"
+
+namespace {
+
+struct DevMem {
+    void* p = nullptr;
+    explicit DevMem(size_t bytes) { ACEMI_HIP(hipMalloc(&p, bytes ? bytes : 16)); }
+    DevMem(const void* host, size_t bytes) : DevMem(bytes) {
+        if (host) ACEMI_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+    }
+    ~DevMem() {
+        if (p) (void)hipFree(p);
+    }
+    DevMem(const DevMem&) = delete;
+    DevMem& operator=(const DevMem&) = delete;
+    template <typename T>
+    T* as() {
+        return static_cast<T*>(p);
+    }
+    void to_host(void* host, size_t bytes) { ACEMI_HIP(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost)); }
+};
+
+constexpr int D = 128;
+
+// what check_post (lm_decode.hip) refuses, plus a row stride that holds the heads
+bool post_args_ok(int B, int hq, int hkv, int capacity, int ld, const void* qkv, const void* k_norm, const void* cs,
+                  const void* sn, const void* kc, const void* vc, const void* km) {
+    return B >= 1 && B <= acemi::LM_MAX_BATCH && hq >= 1 && hkv >= 1 && capacity >= 1 &&
+           (int64_t)ld >= (int64_t)(hq + 2 * hkv) * D && qkv && k_norm && cs && sn && kc && vc && km;
+}
+
+}  // namespace
+
+extern "C" {
+
+ace_ggml_status ace_mi_kernel_lm_skinny(int32_t act_type, int32_t epi, int32_t B, int32_t N, int32_t K, int32_t ldx,
+                                        int32_t ldy, const uint16_t* x, const uint16_t* W, float* y_f32,
+                                        uint16_t* y_u16) {
+    using namespace acemi;
+    if ((act_type != 0 && act_type != 1) || B < 1 || B > LM_MAX_BATCH || N < 1 || K < 8 || K % 8 != 0 || ldx % 8 != 0 ||
+        ldx < K || !x || !W)
+        return ACE_GGML_ERR_INVALID_ARG;
+    const bool swiglu = epi == LM_EPI_SWIGLU;
+    if (swiglu ? (N % 32 != 0 || !y_u16) : ((epi != LM_EPI_STORE && epi != LM_EPI_RESID) || !y_f32))
+        return ACE_GGML_ERR_INVALID_ARG;
+    if (ldy < (swiglu ? N / 2 : N)) return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const size_t ny = (size_t)B * ldy * (swiglu ? 2 : 4);
+        void* y = swiglu ? (void*)y_u16 : (void*)y_f32;
+        DevMem dx(x, (size_t)B * ldx * 2), dW(W, (size_t)N * K * 2), dy(y, ny);
+        launch_lm_skinny(act_type == 1 ? ActType::F16 : ActType::BF16, dx.as<uint16_t>(), ldx, B, dW.as<uint16_t>(), N, K,
+                         epi, swiglu ? nullptr : dy.as<float>(), swiglu ? dy.as<uint16_t>() : nullptr, ldy, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dy.to_host(y, ny);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_skinny: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_kernel_lm_embed(int32_t fmt, int32_t n, int32_t vocab, int32_t H, const uint16_t* table,
+                                       const int32_t* ids, float* out) {
+    using namespace acemi;
+    if ((fmt != 0 && fmt != 1) || n < 1 || vocab < 1 || H < 8 || H % 8 != 0 || !table || !ids || !out)
+        return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const size_t no = (size_t)n * H * 4;
+        DevMem dt(table, (size_t)vocab * H * 2), di(ids, (size_t)n * 4), dout(out, no);
+        launch_lm_embed(dt.p, fmt, di.as<int32_t>(), n, vocab, H, dout.as<float>(), nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dout.to_host(out, no);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_embed: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_kernel_lm_qkv_post(int32_t B, int32_t hq, int32_t hkv, int32_t capacity, int32_t pos, int32_t ld,
+                                          float eps, const float* qkv, const float* q_norm, const float* k_norm,
+                                          const float* rope_cos, const float* rope_sin, const int32_t* mask_new,
+                                          float* q_out, uint16_t* k_cache, uint16_t* v_cache, int32_t* key_mask) {
+    using namespace acemi;
+    if (!post_args_ok(B, hq, hkv, capacity, ld, qkv, k_norm, rope_cos, rope_sin, k_cache, v_cache, key_mask) || !q_norm ||
+        !q_out || pos < 0 || pos >= capacity)
+        return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const size_t nc = (size_t)B * hkv * capacity * D * 2, nm = (size_t)B * capacity * 4, nq = (size_t)B * hq * D * 4;
+        DevMem dqkv(qkv, (size_t)B * ld * 4), dqn(q_norm, D * 4), dkn(k_norm, D * 4);
+        DevMem dcs(rope_cos, (size_t)capacity * 64 * 4), dsn(rope_sin, (size_t)capacity * 64 * 4);
+        DevMem dmn(mask_new, (size_t)B * 4), dq(q_out, nq), dk(k_cache, nc), dv(v_cache, nc), dm(key_mask, nm);
+        LmQkvPostArgs a;
+        a.qkv = dqkv.as<float>();
+        a.ld = ld;
+        a.hq = hq;
+        a.hkv = hkv;
+        a.q_norm = dqn.as<float>();
+        a.k_norm = dkn.as<float>();
+        a.rope_cos = dcs.as<float>();
+        a.rope_sin = dsn.as<float>();
+        a.eps = eps;
+        a.q_out = dq.as<float>();
+        a.k_cache = dk.as<uint16_t>();
+        a.v_cache = dv.as<uint16_t>();
+        a.key_mask = dm.as<int32_t>();
+        a.capacity = capacity;
+        a.pos = pos;
+        a.mask_new = mask_new ? dmn.as<int32_t>() : nullptr;
+        launch_lm_qkv_post(a, B, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dq.to_host(q_out, nq);
+        dk.to_host(k_cache, nc);
+        dv.to_host(v_cache, nc);
+        dm.to_host(key_mask, nm);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_qkv_post: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_kernel_lm_prefill_kv(int32_t B, int32_t hq, int32_t hkv, int32_t capacity, int32_t n, int32_t ld,
+                                            float eps, float* qkv, const float* k_norm, const float* rope_cos,
+                                            const float* rope_sin, const int32_t* mask, uint16_t* k_cache,
+                                            uint16_t* v_cache, int32_t* key_mask) {
+    using namespace acemi;
+    if (!post_args_ok(B, hq, hkv, capacity, ld, qkv, k_norm, rope_cos, rope_sin, k_cache, v_cache, key_mask) || n < 1 ||
+        n > capacity || n > 65535)
+        return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const size_t nc = (size_t)B * hkv * capacity * D * 2, nm = (size_t)B * capacity * 4;
+        const size_t nx = (size_t)B * n * ld * 4;
+        DevMem dqkv(qkv, nx), dkn(k_norm, D * 4);
+        DevMem dcs(rope_cos, (size_t)capacity * 64 * 4), dsn(rope_sin, (size_t)capacity * 64 * 4);
+        DevMem dmask(mask, (size_t)B * n * 4), dk(k_cache, nc), dv(v_cache, nc), dm(key_mask, nm);
+        LmQkvPostArgs a;
+        a.qkv = dqkv.as<float>();
+        a.ld = ld;
+        a.hq = hq;
+        a.hkv = hkv;
+        a.q_norm = dkn.as<float>();  // unused by the prefill fill; check_post wants a pointer
+        a.k_norm = dkn.as<float>();
+        a.rope_cos = dcs.as<float>();
+        a.rope_sin = dsn.as<float>();
+        a.eps = eps;
+        a.k_cache = dk.as<uint16_t>();
+        a.v_cache = dv.as<uint16_t>();
+        a.key_mask = dm.as<int32_t>();
+        a.capacity = capacity;
+        launch_lm_prefill_kv(a, B, n, mask ? dmask.as<int32_t>() : nullptr, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dqkv.to_host(qkv, nx);
+        dk.to_host(k_cache, nc);
+        dv.to_host(v_cache, nc);
+        dm.to_host(key_mask, nm);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_prefill_kv: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_kernel_lm_attention(int32_t out_type, int32_t B, int32_t hq, int32_t hkv, int32_t capacity,
+                                           int32_t nk, float scale, const float* q, const uint16_t* k_cache,
+                                           const uint16_t* v_cache, const int32_t* key_mask, uint16_t* out_u16) {
+    using namespace acemi;
+    if ((out_type != 0 && out_type != 1) || B < 1 || B > LM_MAX_BATCH || hkv < 1 || hq < 1 || hq % hkv != 0 || nk < 1 ||
+        nk > capacity || !q || !k_cache || !v_cache || !key_mask || !out_u16)
+        return ACE_GGML_ERR_INVALID_ARG;
+    const int rep = hq / hkv;
+    if (rep != 1 && rep != 2 && rep != 4) return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const size_t nc = (size_t)B * hkv * capacity * D * 2, no = (size_t)B * hq * D * 2;
+        DevMem dq(q, (size_t)B * hq * D * 4), dk(k_cache, nc), dv(v_cache, nc), dm(key_mask, (size_t)B * capacity * 4);
+        DevMem dout(out_u16, no), dpart(lm_attn_part_floats(B, hq, nk) * 4);
+        LmAttnArgs a;
+        a.q = dq.as<float>();
+        a.k_cache = dk.as<uint16_t>();
+        a.v_cache = dv.as<uint16_t>();
+        a.key_mask = dm.as<int32_t>();
+        a.hkv = hkv;
+        a.capacity = capacity;
+        a.nk = nk;
+        a.scale = scale;
+        a.out = dout.as<uint16_t>();
+        a.part = dpart.as<float>();
+        launch_lm_attention(out_type == 1 ? ActType::F16 : ActType::BF16, a, B, hq, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dout.to_host(out_u16, no);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_attention: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+}  // extern "C"

@@ -104,6 +104,39 @@ typedef struct ace_mi_lora_job {
 ACE_GGML_API ace_ggml_status ace_mi_kernel_lora_merge(int32_t fmt, int32_t total_rows, int32_t cols, int32_t ld_base,
                                                       int32_t ld_out, const uint16_t* base, uint16_t* out,
                                                       const ace_mi_lora_job* jobs, int32_t n_jobs);
+/* ---- LM decode kernels (csrc/kernels/lm_decode.hip through launch_lm_* of csrc/kernels.h; csrc/runtime/selftest_lm.cpp).
+ * One launch_lm_* call each on host buffers; INVALID_ARG, before any allocation, for what the launch entry refuses or
+ * what does not fit the host buffers.  16-bit words are raw bf16 (type / fmt 0) or fp16 (1).
+ * Skinny product y[B][N] = x[B][K] . W[N][K]^T: x [B][ldx], W [N][K]; epi 0 store / 1 add into y_f32 [B][ldy]; epi 2
+ * SwiGLU on the 16-row interleaved gate|up W into y_u16 [B][ldy] (N / 2 columns).  y_* holds its initial content on
+ * entry and is copied back whole, padding columns included. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_skinny(int32_t act_type, int32_t epi, int32_t B, int32_t N, int32_t K,
+                                                     int32_t ldx, int32_t ldy, const uint16_t* x, const uint16_t* W,
+                                                     float* y_f32, uint16_t* y_u16);
+/* Embedding rows: out [n][H] f32 = table [vocab][H] at ids [n] clamped into the table. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_embed(int32_t fmt, int32_t n, int32_t vocab, int32_t H,
+                                                    const uint16_t* table, const int32_t* ids, float* out);
+/* Decode step's q/k norm + RoPE + cache append at slot pos: qkv [B][ld] f32, q_norm / k_norm [128], rope_cos / rope_sin
+ * [capacity][64], mask_new [B] or NULL; q_out [B][hq][128] f32; k_cache / v_cache [B][hkv][capacity][128] fp16 and
+ * key_mask [B][capacity] (one layer) are in-out. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_qkv_post(int32_t B, int32_t hq, int32_t hkv, int32_t capacity, int32_t pos,
+                                                       int32_t ld, float eps, const float* qkv, const float* q_norm,
+                                                       const float* k_norm, const float* rope_cos,
+                                                       const float* rope_sin, const int32_t* mask_new, float* q_out,
+                                                       uint16_t* k_cache, uint16_t* v_cache, int32_t* key_mask);
+/* Prefill cache fill of rows b * n + t of qkv [B * n][ld] (in-out: padding rows are zeroed) into slots t < n; mask
+ * [B][n] or NULL; caches and key_mask as above. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_prefill_kv(int32_t B, int32_t hq, int32_t hkv, int32_t capacity, int32_t n,
+                                                         int32_t ld, float eps, float* qkv, const float* k_norm,
+                                                         const float* rope_cos, const float* rope_sin,
+                                                         const int32_t* mask, uint16_t* k_cache, uint16_t* v_cache,
+                                                         int32_t* key_mask);
+/* Decode attention over keys 0 .. nk-1 of the cache: q [B][hq][128] f32, out_u16 [B][hq * 128] words of out_type; the
+ * split workspace (lm_attn_part_floats) is allocated here. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_attention(int32_t out_type, int32_t B, int32_t hq, int32_t hkv,
+                                                        int32_t capacity, int32_t nk, float scale, const float* q,
+                                                        const uint16_t* k_cache, const uint16_t* v_cache,
+                                                        const int32_t* key_mask, uint16_t* out_u16);
 /* Dequant-fused GEMM micro-benchmark: average ms per launch (HIP events). */
 ACE_GGML_API ace_ggml_status ace_mi_bench_gemm_q(int32_t qtype, int32_t epi, int32_t variant, int32_t M, int32_t N,
                                                  int32_t K, int32_t iters, float* avg_ms);

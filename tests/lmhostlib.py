@@ -7,7 +7,7 @@ import tempfile
 
 from hostlib import CLANG, CSRC, ROOT, RUNTIME
 
-LM_RUNTIME = RUNTIME + ("lm.cpp",)
+LM_RUNTIME = RUNTIME + ("lm.cpp", "selftest_lm.cpp")   # selftest_lm.cpp: the ace_mi_kernel_lm_* entries over lm_emul.cpp
 EMUL = ("kernel_emul.cpp", "lm_emul.cpp")
 
 
