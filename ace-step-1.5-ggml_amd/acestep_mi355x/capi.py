@@ -53,7 +53,8 @@ SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_ben
                     "ace_mi_kernel_dequant_blocks", "ace_mi_kernel_dequant_segments", "ace_mi_bench_dequant_blocks",
                     "ace_mi_gemm_resolve", "ace_mi_gemm_variant_row", "ace_mi_gemm_variant_arg_ok",
                     "ace_mi_kernel_lm_skinny", "ace_mi_kernel_lm_embed", "ace_mi_kernel_lm_qkv_post",
-                    "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention")
+                    "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention", "ace_mi_kernel_lm_skinny_q",
+                    "ace_mi_kernel_lm_embed_q")
 
 # qtype codes of ace_mi_quantize & co. (names as parse_quant_type, acestep_dit_model.cpp:27-37)
 QTYPES = {"q8_0": 1, "q4_k": 2, "q6_k": 3,
@@ -933,7 +934,10 @@ def _bind_lm_kernels(lib):
     lib.ace_mi_kernel_lm_qkv_post.argtypes = [i32] * 6 + [f32, fp, fp, fp, fp, fp, ip, fp, u16p, u16p, ip]
     lib.ace_mi_kernel_lm_prefill_kv.argtypes = [i32] * 6 + [f32, fp, fp, fp, fp, ip, u16p, u16p, ip]
     lib.ace_mi_kernel_lm_attention.argtypes = [i32] * 6 + [f32, fp, u16p, u16p, ip, u16p]
-    for name in ("skinny", "embed", "qkv_post", "prefill_kv", "attention"):
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    lib.ace_mi_kernel_lm_skinny_q.argtypes = [i32] * 8 + [u16p, u8p, fp, u16p, ip]
+    lib.ace_mi_kernel_lm_embed_q.argtypes = [i32] * 4 + [u8p, ip, fp]
+    for name in ("skinny", "embed", "qkv_post", "prefill_kv", "attention", "skinny_q", "embed_q"):
         getattr(lib, "ace_mi_kernel_lm_" + name).restype = ctypes.c_int
     return lib
 
@@ -976,6 +980,47 @@ def kernel_lm_embed(table_bits: np.ndarray, ids: np.ndarray, fmt: int = 0, lib=N
     out = np.full((i.shape[0], t.shape[1]), np.nan, dtype=np.float32)
     _lm_status("embed", lib.ace_mi_kernel_lm_embed(fmt, i.shape[0], t.shape[0], t.shape[1], _u16ptr(t), _iptr(i),
                                                    _fptr(out)))
+    return out
+
+
+def _block_rows(blocks: np.ndarray, qtype: str):
+    """uint8 [rows][nb][block bytes] -> (contiguous array, rows, K)"""
+    b = np.ascontiguousarray(blocks, dtype=np.uint8)
+    qk, bb = _BLOCK[qtype]
+    if b.ndim != 3 or b.shape[2] != bb:
+        raise ValueError(f"{qtype} blocks must be [rows][nb][{bb}]")
+    return b, b.shape[0], b.shape[1] * qk
+
+
+def kernel_lm_skinny_q(x_bits: np.ndarray, blocks: np.ndarray, qtype: str, y0: np.ndarray, epi: int = 0, n_rows=None,
+                       lib=None, with_chain: bool = False):
+    """launch_lm_skinny_q on host arrays: x_bits [B][ldx] bf16 words, blocks uint8 [rows][K / block][block bytes] ggml
+    blocks of qtype ("q8_0", "q4_k", "q6_k"), re-laid out into the loader's planes by the entry; n_rows (default: all)
+    is the N of the product, rows past it are uploaded but must not be read.  y0 as kernel_lm_skinny.  Returns the
+    destination after the launch, padding included (with_chain: and the kernel's longest f32 addition chain)."""
+    lib = _lm_lib(lib)
+    x = np.ascontiguousarray(x_bits, dtype=np.uint16)
+    b, rows, K = _block_rows(blocks, qtype)
+    N = rows if n_rows is None else int(n_rows)
+    y = np.array(y0, dtype=np.uint16 if epi == LM_EPI_SWIGLU else np.float32, order="C", copy=True)
+    chain = ctypes.c_int32(0)
+    st = lib.ace_mi_kernel_lm_skinny_q(QTYPES[qtype], epi, x.shape[0], N, rows, K, x.shape[1], y.shape[1], _u16ptr(x),
+                                       b.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                       None if epi == LM_EPI_SWIGLU else _fptr(y),
+                                       _u16ptr(y) if epi == LM_EPI_SWIGLU else None, ctypes.byref(chain))
+    _lm_status("skinny_q", st)
+    return (y, int(chain.value)) if with_chain else y
+
+
+def kernel_lm_embed_q(blocks: np.ndarray, qtype: str, ids: np.ndarray, lib=None) -> np.ndarray:
+    """launch_lm_embed_q: blocks uint8 [vocab][H / block][block bytes] of qtype, ids [n] int32 -> f32 [n][H]."""
+    lib = _lm_lib(lib)
+    b, vocab, H = _block_rows(blocks, qtype)
+    i = np.ascontiguousarray(ids, dtype=np.int32)
+    out = np.full((i.shape[0], H), np.nan, dtype=np.float32)
+    _lm_status("embed_q", lib.ace_mi_kernel_lm_embed_q(QTYPES[qtype], i.shape[0], vocab, H,
+                                                       b.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _iptr(i),
+                                                       _fptr(out)))
     return out
 
 

@@ -514,6 +514,42 @@ def write_gguf_tensors(out_path: str, tensors, arch: str = "acestep") -> str:
     return _write_gguf_entries([(n, sh, GGML_TYPES[t], data) for n, (sh, t, data) in tensors.items()], out_path, arch)
 
 
+# Tiny causal-LM GGUFs (ace_mi_load_lm): a type per projection, HF tensor names, norms in F32.
+LM_GGUF_VARIANTS = {
+    "q8_0": dict(tied=False, types="Q8_0"),
+    "q4_k": dict(tied=True, types="Q4_K"),
+    "q6_k": dict(tied=True, types="Q6_K"),
+    # a fused QKV of differing types and a type without planes (o_proj): both become bf16 images
+    "mixed": dict(tied=True, types=dict(q_proj="Q4_K", k_proj="Q4_K", gate_proj="Q4_K", up_proj="Q4_K", v_proj="Q6_K",
+                                        down_proj="Q6_K", o_proj="Q5_K", embed_tokens="Q6_K")),
+}
+
+
+def write_lm_gguf(out_dir: str, types, tied: bool = True, seed: int = 7, cfg: Optional[dict] = None,
+                  model_prefix: bool = True, file_name: str = "model.gguf") -> str:
+    """config.json + a GGUF of the tiny causal LM of write_lm_checkpoint(seed, tied): `types` is one type name for every
+    2-D tensor, or a dict keyed by the tensor's module (q_proj, ..., embed_tokens, lm_head; a missing key: F16) -- the
+    per-tensor map handed to write_gguf_typed, whose encoders / random blocks make the bytes; 1-D tensors (norms) are
+    F32.  Deterministic in (types, tied, seed).  Returns the GGUF's path."""
+    import tempfile
+    src = tempfile.mkdtemp(prefix="acemi_lm_gguf_src_")
+    write_lm_checkpoint(src, cfg=cfg, seed=seed, tied=tied, model_prefix=model_prefix)
+
+    def pick(name, shape):
+        if len(shape) < 2:
+            return "F32"
+        if isinstance(types, str):
+            return types
+        return types.get(name.split(".")[-2])
+
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(src, "config.json"), "rb") as f, open(os.path.join(out_dir, "config.json"), "wb") as g:
+        g.write(f.read())
+    out = os.path.join(out_dir, file_name)
+    write_gguf_typed(os.path.join(src, "model.safetensors"), out, pick, seed=seed)
+    return out
+
+
 # ----------------------------------------------------------------------------- PEFT LoRA adapters
 # What peft's save_pretrained writes for the reference trainer (acestep/training/lora_utils.py, configs.py:12-38:
 # r = 8, alpha = 16, targets q_proj,k_proj,v_proj,o_proj): adapter_config.json + adapter_model.safetensors with

@@ -367,6 +367,19 @@ void launch_lm_skinny(ActType t, const uint16_t* x, int ldx, int B, const uint16
 // launch_embed_rows for a 16-bit table (fmt 0 bf16, 1 fp16) with the ids (device values nobody validated) clamped
 // into [0, vocab)
 void launch_lm_embed(const void* table, int fmt, const int32_t* ids, int n, int vocab, int H, float* out, hipStream_t s);
+// The same two operations on a weight in ggml block planes (kernels/lm_decode_q.hip; plane layout: runtime/quant.h).
+// launch_lm_skinny_q: x bf16, W.fmt WF_Q8_0 / WF_Q4_K / WF_Q6_K, K % 32 == 0 (Q8_0) or K % 256 == 0 (K-quants); the
+// weight value multiplied is the bf16 rounding of the plane dequant (the value the quantized GEMMs of gemm_q.hip
+// multiply), the epilogues and the fixed reduction order are launch_lm_skinny's.
+void launch_lm_skinny_q(const uint16_t* x, int ldx, int B, const WeightView& W, int N, int K, int epi, float* y_f32,
+                        uint16_t* y_act, int ldy, hipStream_t s);
+// longest f32 addition chain behind one output of launch_lm_skinny_q (its lane mapping: lm_decode_q.hip's header)
+int lm_skinny_q_chain(int fmt, int K);
+// launch_lm_embed_q: rows of the planes as ggml's get_rows returns them (the f32 dequant, not rounded to bf16), ids
+// clamped into [0, vocab).  fmt LM_EMBED_F32: `q` is an f32 table [vocab][H] (a table without a plane layout).
+constexpr int LM_EMBED_F32 = 100;
+void launch_lm_embed_q(int fmt, const void* q, const float* s, const int32_t* ids, int n, int vocab, int H, float* out,
+                       hipStream_t stream);
 // KV cache of one layer: k_cache / v_cache [B][hkv][capacity][128] fp16, key_mask [B][capacity] int32 (shared by the
 // layers).  qkv: the fused projection's f32 rows [.][ld] = [q heads | k heads | v heads]; rope_cos / rope_sin
 // [capacity][64].

@@ -5,7 +5,9 @@
 //   prefill (n > 1, empty cache)  the text encoder's path: BlockRunner (MFMA GEMMs, causal flash attention, key mask);
 //                                 its after-QKV hook stores every layer's post-norm, post-RoPE K and V into the cache.
 //   decode step (n == 1)          kernels/lm_decode.hip: skinny products over the same fused matrices DevLayer holds,
-//                                 QKV post-processing, decode attention over the cache.
+//                                 QKV post-processing, decode attention over the cache.  A matrix in ggml block planes
+//                                 (a GGUF checkpoint's Q8_0 / Q4_K / Q6_K tensors) goes through kernels/lm_decode_q.hip,
+//                                 which multiplies the bf16 values the prefill's quantized GEMM multiplies.
 // Rounding points follow BlockRunner::run: the residual stream stays f32, the input of every linear is rounded to
 // the weights' 16-bit type, products accumulate in f32.  The one deviation: prefill attention reads Q, K, V as fp16
 // hi + lo pairs (~22 bits), the decode step keeps Q in f32 and reads K and V from the cache as single fp16 values.
@@ -14,6 +16,7 @@
 #include <cmath>
 #include <vector>
 
+#include "../kernels/lm_decode_q_host.h"  // empty under hipcc; the host build's launch_lm_skinny_q / launch_lm_embed_q
 #include "context.h"
 #include "safetensors.h"
 
@@ -66,10 +69,15 @@ class LmEngine {
     }
 
     void check_weights() const {
+        auto ok = [](const DevWeight& w) { return (w.fmt == WF_BF16 || w.fmt == WF_F16 || weight_planes(w.fmt)) && w.q; };
         for (const DevLayer& ly : model_.layers)
             for (const DevWeight* w : {&ly.w_qkv, &ly.w_o, &ly.w_gu, &ly.w_down})
-                if (w->fmt != WF_BF16 && w->fmt != WF_F16) throw Unsupported("LM weights must be dense BF16 / F16");
-        if (!model_.head || model_.embed_fmt == 2) throw Unsupported("LM head / embed table must be 16-bit");
+                if (!ok(*w)) throw Unsupported("LM weights must be dense BF16 / F16 or Q8_0 / Q4_K / Q6_K planes");
+        if (!ok(model_.head)) throw Unsupported("LM head must be dense BF16 / F16 or Q8_0 / Q4_K / Q6_K planes");
+        for (const DevLayer& ly : model_.layers)
+            for (const DevWeight* w : {&ly.w_qkv, &ly.w_o, &ly.w_gu, &ly.w_down})
+                if (weight_planes(w->fmt) && model_.act != ActType::BF16)
+                    throw Unsupported("mixed LM weight types: block planes take BF16 activations");
     }
 
     void begin(int B, int cap) {
@@ -145,13 +153,31 @@ class LmEngine {
         return a;
     }
 
+    // one skinny product of the step, by the matrix's format: dense 16-bit rows or block planes
+    void skinny(ActType t, const uint16_t* x, int ldx, const DevWeight& w, int N, int K, int epi, float* y_f32,
+                uint16_t* y_act, int ldy, hipStream_t s) {
+        if (weight_planes(w.fmt))
+            launch_lm_skinny_q(x, ldx, batch_, w.view(), N, K, epi, y_f32, y_act, ldy, s);
+        else
+            launch_lm_skinny(t, x, ldx, batch_, static_cast<const uint16_t*>(w.q), N, K, epi, y_f32, y_act, ldy, s);
+    }
+
+    void embed(const int32_t* d_ids, int n, float* x, hipStream_t s) {
+        const TextConfig& c = model_.cfg;
+        if (model_.embed_fmt == 3)
+            launch_lm_embed_q(model_.embed_q.fmt, model_.embed_q.q, model_.embed_q.s, d_ids, n, c.vocab, c.hidden, x, s);
+        else if (model_.embed_fmt == 2)
+            launch_lm_embed_q(LM_EMBED_F32, model_.embed, nullptr, d_ids, n, c.vocab, c.hidden, x, s);
+        else
+            launch_lm_embed(model_.embed, model_.embed_fmt, d_ids, n, c.vocab, c.hidden, x, s);
+    }
+
     void head(const float* x_last, int64_t row_step, float* d_logits, hipStream_t s) {
         const TextConfig& c = model_.cfg;
-        const ActType ht = model_.head_fmt == 1 ? ActType::F16 : ActType::BF16;
+        const ActType ht = model_.head.act();
         launch_rmsnorm_f32(x_last, batch_, row_step, c.hidden, model_.norm, c.eps, xn_.as<float>(), s);
         launch_to_act(ht, xn_.as<float>(), (int64_t)batch_ * c.hidden, false, xh_.as<uint16_t>(), s);
-        launch_lm_skinny(ht, xh_.as<uint16_t>(), c.hidden, batch_, static_cast<const uint16_t*>(model_.head), c.vocab,
-                         c.hidden, LM_EPI_STORE, d_logits, nullptr, c.vocab, s);
+        skinny(ht, xh_.as<uint16_t>(), c.hidden, model_.head, c.vocab, c.hidden, LM_EPI_STORE, d_logits, nullptr, c.vocab, s);
     }
 
     BlockShape shape() const {
@@ -172,7 +198,7 @@ class LmEngine {
         const BlockShape sh = shape();
         const int M = batch_ * n;
         float* x = blocks_.x(M, sh.hidden);
-        launch_lm_embed(model_.embed, model_.embed_fmt, d_ids, M, c.vocab, sh.hidden, x, s);
+        embed(d_ids, M, x, s);
         const BlockRunner::AfterQkv fill = [&](int li, float* qkv, int ld) {
             launch_lm_prefill_kv(post_args(li, qkv, ld), batch_, n, d_mask, s);
         };
@@ -189,12 +215,11 @@ class LmEngine {
         uint16_t* act2 = act2_.as<uint16_t>();
         uint16_t* attn = attn_.as<uint16_t>();
         float* qkv = qkv_.as<float>();
-        launch_lm_embed(model_.embed, model_.embed_fmt, d_ids, B, c.vocab, H, x, s);
+        embed(d_ids, B, x, s);
         for (int li = 0; li < c.layers; ++li) {
             const DevLayer& ly = model_.layers[li];
             launch_rmsnorm_mod(at, x, B, H, ly.self_norm, nullptr, nullptr, 0, 1, c.eps, act, s);
-            launch_lm_skinny(at, act, H, B, static_cast<const uint16_t*>(ly.w_qkv.q), qd + 2 * kd, H, LM_EPI_STORE, qkv,
-                             nullptr, qd + 2 * kd, s);
+            skinny(at, act, H, ly.w_qkv, qd + 2 * kd, H, LM_EPI_STORE, qkv, nullptr, qd + 2 * kd, s);
             LmQkvPostArgs pa = post_args(li, qkv, qd + 2 * kd);
             pa.pos = len_;
             pa.mask_new = d_mask;
@@ -211,11 +236,10 @@ class LmEngine {
             aa.out = attn;
             aa.part = part_.as<float>();
             launch_lm_attention(at, aa, B, c.hq, s);
-            launch_lm_skinny(at, attn, qd, B, static_cast<const uint16_t*>(ly.w_o.q), H, qd, LM_EPI_RESID, x, nullptr, H, s);
+            skinny(at, attn, qd, ly.w_o, H, qd, LM_EPI_RESID, x, nullptr, H, s);
             launch_rmsnorm_mod(at, x, B, H, ly.mlp_norm, nullptr, nullptr, 0, 1, c.eps, act, s);
-            launch_lm_skinny(at, act, H, B, static_cast<const uint16_t*>(ly.w_gu.q), 2 * I, H, LM_EPI_SWIGLU, nullptr, act2,
-                             I, s);
-            launch_lm_skinny(at, act2, I, B, static_cast<const uint16_t*>(ly.w_down.q), H, I, LM_EPI_RESID, x, nullptr, H, s);
+            skinny(at, act, H, ly.w_gu, 2 * I, H, LM_EPI_SWIGLU, nullptr, act2, I, s);
+            skinny(at, act2, I, ly.w_down, H, I, LM_EPI_RESID, x, nullptr, H, s);
         }
         head(x, 1, d_logits, s);
     }
@@ -246,7 +270,7 @@ ace_ggml_status ace_mi_load_lm(ace_ggml_context* ctx, const char* model_dir) {
         acemi::TextLoadOptions opt;
         opt.model_prefix = true;
         opt.lm_head = true;
-        opt.dense16_only = true;
+        opt.lm_checkpoint = true;
         acemi::load_text_model(model_dir, eng->model(), opt);
         eng->check_weights();
         ctx->lm = std::move(eng);

@@ -1,13 +1,16 @@
-// Kernel self-test entries of the LM decode kernels (kernels/lm_decode.hip; include/acestep_mi355x_selftest.h): one
+// Kernel self-test entries of the LM decode kernels (kernels/lm_decode.hip, kernels/lm_decode_q.hip;
+// include/acestep_mi355x_selftest.h): one
 // launch_lm_* call on host buffers, blocking, so that tests/lm_kernel_cases.py can compare each kernel with a float64
 // reference of the same operation.  Built into libacestep_mi355x_selftest.so (Makefile target `selftest`) and, on top
 // of tests/host/lm_emul.cpp, into the LM host library (tests/lmhostlib.py); not part of runtime/selftest.cpp, which the
 // host library of tests/hostlib.py compiles without the LM kernels.
 #include <cstdio>
 #include <cstring>
+#include <vector>
 
 #include "../../../include/acestep_mi355x_selftest.h"
 #include "../kernels.h"
+#include "quant.h"
 
 namespace {
 
@@ -38,9 +41,84 @@ bool post_args_ok(int B, int hq, int hkv, int capacity, int ld, const void* qkv,
            (int64_t)ld >= (int64_t)(hq + 2 * hkv) * D && qkv && k_norm && cs && sn && kc && vc && km;
 }
 
+// ggml block rows -> the loader's planes (Loader::from_blocks) on the device
+struct DevPlanes {
+    DevMem q, s;
+    int fmt;
+    DevPlanes(acemi::quant::QType t, const std::vector<uint8_t>& qp, const std::vector<float>& sp)
+        : q(qp.data(), qp.size()), s(sp.data(), sp.size() * 4),
+          fmt(t == acemi::quant::Q8_0 ? acemi::WF_Q8_0 : (t == acemi::quant::Q4_K ? acemi::WF_Q4_K : acemi::WF_Q6_K)) {}
+};
+
+// qtype: the quant::QType ids 1 Q8_0, 2 Q4_K, 3 Q6_K (as ace_mi_quantize takes them)
+bool plane_type_ok(int qtype, int K) {
+    const auto t = static_cast<acemi::quant::QType>(qtype);
+    return qtype >= 1 && qtype <= 3 && acemi::quant::has_planes(t) && K >= acemi::quant::block_values(t) &&
+           K % acemi::quant::block_values(t) == 0;
+}
+
 }  // namespace
 
 extern "C" {
+
+ace_ggml_status ace_mi_kernel_lm_skinny_q(int32_t qtype, int32_t epi, int32_t B, int32_t N, int32_t w_rows, int32_t K,
+                                          int32_t ldx, int32_t ldy, const uint16_t* x, const uint8_t* blocks,
+                                          float* y_f32, uint16_t* y_u16, int32_t* chain) {
+    using namespace acemi;
+    if (!plane_type_ok(qtype, K) || B < 1 || B > LM_MAX_BATCH || N < 1 || w_rows < N || ldx % 8 != 0 || ldx < K || !x ||
+        !blocks)
+        return ACE_GGML_ERR_INVALID_ARG;
+    const bool swiglu = epi == LM_EPI_SWIGLU;
+    if (swiglu ? (N % 32 != 0 || !y_u16) : ((epi != LM_EPI_STORE && epi != LM_EPI_RESID) || !y_f32))
+        return ACE_GGML_ERR_INVALID_ARG;
+    if (ldy < (swiglu ? N / 2 : N)) return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const auto t = static_cast<quant::QType>(qtype);
+        std::vector<uint8_t> qp(quant::q_plane_bytes(t, w_rows, K));
+        std::vector<float> sp(quant::s_plane_floats(t, w_rows, K));
+        quant::to_planes(t, blocks, w_rows, K, qp.data(), sp.data());
+        const size_t ny = (size_t)B * ldy * (swiglu ? 2 : 4);
+        void* y = swiglu ? (void*)y_u16 : (void*)y_f32;
+        DevPlanes dW(t, qp, sp);
+        DevMem dx(x, (size_t)B * ldx * 2), dy(y, ny);
+        WeightView W;
+        W.fmt = dW.fmt;
+        W.q = dW.q.p;
+        W.s = dW.s.as<float>();
+        W.ld = K;
+        launch_lm_skinny_q(dx.as<uint16_t>(), ldx, B, W, N, K, epi, swiglu ? nullptr : dy.as<float>(),
+                           swiglu ? dy.as<uint16_t>() : nullptr, ldy, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dy.to_host(y, ny);
+        if (chain) *chain = lm_skinny_q_chain(dW.fmt, K);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_skinny_q: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_kernel_lm_embed_q(int32_t qtype, int32_t n, int32_t vocab, int32_t H, const uint8_t* blocks,
+                                         const int32_t* ids, float* out) {
+    using namespace acemi;
+    if (!plane_type_ok(qtype, H) || n < 1 || vocab < 1 || !blocks || !ids || !out) return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const auto t = static_cast<quant::QType>(qtype);
+        std::vector<uint8_t> qp(quant::q_plane_bytes(t, vocab, H));
+        std::vector<float> sp(quant::s_plane_floats(t, vocab, H));
+        quant::to_planes(t, blocks, vocab, H, qp.data(), sp.data());
+        const size_t no = (size_t)n * H * 4;
+        DevPlanes dW(t, qp, sp);
+        DevMem di(ids, (size_t)n * 4), dout(out, no);
+        launch_lm_embed_q(dW.fmt, dW.q.p, dW.s.as<float>(), di.as<int32_t>(), n, vocab, H, dout.as<float>(), nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dout.to_host(out, no);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_embed_q: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
 
 ace_ggml_status ace_mi_kernel_lm_skinny(int32_t act_type, int32_t epi, int32_t B, int32_t N, int32_t K, int32_t ldx,
                                         int32_t ldy, const uint16_t* x, const uint16_t* W, float* y_f32,

@@ -51,10 +51,12 @@ void load_text_config(const std::string& path, TextConfig& c) {  // qwen_config.
     }
 }
 
-// resolve_gguf_path (qwen_model.cpp:46-72)
-std::string resolve_text_gguf(const std::string& dir) {
+// resolve_gguf_path (qwen_model.cpp:46-72).  lm: ace_mi_load_lm's entry, which consults ACE_GGML_LM_GGUF alone -- a
+// process that points the text encoder at its file through one of the other two keys keeps the LM on its own checkpoint.
+std::string resolve_text_gguf(const std::string& dir, bool lm) {
     namespace fs = std::filesystem;
     for (const char* key : {"ACE_GGML_QWEN_GGUF", "ACE_GGML_TEXT_ENCODER_GGUF", "ACE_GGML_LM_GGUF"}) {
+        if (lm && std::string(key) != "ACE_GGML_LM_GGUF") continue;
         const char* v = std::getenv(key);
         if (v && v[0] && fs::exists(v)) return v;
     }
@@ -70,12 +72,11 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
     namespace fs = std::filesystem;
     const fs::path p(dir);
     const fs::path root = p.extension() == ".gguf" ? p.parent_path() : p;
-    const std::string gguf_path = resolve_text_gguf(dir);
-    if (opt.dense16_only) {
-        if (!gguf_path.empty()) throw Unsupported("quantized LM weights are not supported: GGUF checkpoint " + gguf_path);
-        if (quant::from_env("ACE_GGML_QWEN_WEIGHT_QTYPE") != quant::QNONE)
-            throw Unsupported("quantized LM weights are not supported: unset ACE_GGML_QWEN_WEIGHT_QTYPE (16-bit BF16 / F16 only)");
-    }
+    const std::string gguf_path = resolve_text_gguf(dir, opt.lm_checkpoint);
+    // online quantization of the LM is not built: with a GGUF the variable is ignored (the file's types hold, as in
+    // the reference), with safetensors it is refused
+    if (opt.lm_checkpoint && gguf_path.empty() && quant::from_env("ACE_GGML_QWEN_WEIGHT_QTYPE") != quant::QNONE)
+        throw Unsupported("quantized LM weights are not supported: unset ACE_GGML_QWEN_WEIGHT_QTYPE (16-bit BF16 / F16 only)");
     TextConfig& c = m.cfg;
     load_text_config((root / "config.json").string(), c);
     if (c.head_dim != 128) throw Unsupported("text encoder head_dim must be 128");
@@ -94,6 +95,13 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
     if (!gguf_path.empty()) {
         L.gguf = true;
         L.gg.open(gguf_path);
+        if (opt.model_prefix) {  // the same names under "model." (HF Qwen3ForCausalLM), as for safetensors below
+            std::vector<std::pair<std::string, GgufTensor>> bare;
+            for (const auto& kv : L.gg.tensors)
+                if (kv.first.rfind("model.", 0) == 0 && !L.gg.has(kv.first.substr(6)))
+                    bare.emplace_back(kv.first.substr(6), kv.second);
+            for (auto& kv : bare) L.gg.tensors[kv.first] = kv.second;
+        }
     } else {
         L.st.open((root / "model.safetensors").string());
         if (opt.model_prefix) {  // HF Qwen3ForCausalLM names: "model.layers.0...." beside "lm_head.weight"
@@ -107,15 +115,18 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
     const int H = c.hidden, I = c.intermediate, D = c.head_dim, qd = c.hq * D, kd = c.hkv * D;
     {  // embed_tokens: ggml_get_rows + cast_f32 yields the stored values (dequantized if quantized)
         const Mat e = L.mat("embed_tokens.weight", c.vocab, H);
-        if (e.dtype == "BF16" || e.dtype == "F16") {
+        if (opt.lm_checkpoint && e.dtype == "Q") {  // the gather reads rows of the planes; a tied head shares them
+            m.embed_q = L.from_blocks(e.qt, e.qblocks.data(), e.rows, e.cols);
+            m.embed_fmt = 3;
+        } else if (e.dtype == "BF16" || e.dtype == "F16") {
             if (!quant::applies(L.qt, H)) {
                 m.embed_fmt = e.dtype == "BF16" ? 0 : 1;
                 m.embed = L.upload<uint16_t>(e.u16.data(), e.u16.size() * 2);
             }
         }
-        if (!m.embed && opt.dense16_only)
+        if (!m.embed && m.embed_fmt != 3 && opt.lm_checkpoint && !L.gguf)
             throw Unsupported("LM embed_tokens.weight has dtype " + e.dtype + " (16-bit BF16 / F16 only)");
-        if (!m.embed) {
+        if (!m.embed && m.embed_fmt != 3) {
             std::vector<float> v = L.values(e);
             if (e.dtype != "Q" && quant::applies(L.qt, H)) {  // quantized at load, read back by get_rows
                 std::vector<uint8_t> blocks((size_t)c.vocab * quant::row_bytes(L.qt, H));
@@ -124,6 +135,21 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
             }
             m.embed_fmt = 2;
             m.embed = L.upload<float>(v.data(), v.size() * 4);
+        }
+        if (opt.lm_head && !L.has("lm_head.weight") && c.tie_word_embeddings != 0) {  // the tied head: the table itself
+            if (m.embed_fmt == 3) {
+                m.head = m.embed_q;
+            } else if (m.embed_fmt != 2) {
+                m.head.fmt = m.embed_fmt == 1 ? WF_F16 : WF_BF16;
+                m.head.q = m.embed;
+                m.head.rows = c.vocab;
+                m.head.cols = H;
+            } else if (e.dtype == "R") {  // a block type without planes: f32 rows for the gather, the bf16 image here
+                m.head = L.finish(e);
+            } else {
+                throw Unsupported("a tied LM head needs a 16-bit embed_tokens.weight");
+            }
+            m.tied = true;
         }
     }
     m.norm = L.vec_f32("norm.weight", H);
@@ -144,20 +170,18 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
         ly.w_gu = L.gate_up(p2, I, H);
         ly.w_down = L.finish(L.mat(p2 + "mlp.down_proj.weight", H, I));
     }
-    if (opt.lm_head) {
-        if (L.has("lm_head.weight")) {
-            const Mat hw = L.mat("lm_head.weight", c.vocab, H);
-            if (hw.dtype != "BF16" && hw.dtype != "F16")
-                throw Unsupported("LM lm_head.weight has dtype " + hw.dtype + " (16-bit BF16 / F16 only)");
-            m.head_fmt = hw.dtype == "BF16" ? 0 : 1;
-            m.head = L.upload<uint16_t>(hw.u16.data(), hw.u16.size() * 2);
-        } else if (c.tie_word_embeddings == 0) {
-            throw IoError("missing tensor: lm_head.weight (tie_word_embeddings is false)");
+    if (opt.lm_head && !m.tied) {
+        if (!L.has("lm_head.weight")) throw IoError("missing tensor: lm_head.weight (tie_word_embeddings is false)");
+        const Mat hw = L.mat("lm_head.weight", c.vocab, H);
+        if (hw.dtype == "BF16" || hw.dtype == "F16") {  // its own 16-bit type: the head rounds its input itself
+            m.head.fmt = hw.dtype == "F16" ? WF_F16 : WF_BF16;
+            m.head.q = L.upload<uint16_t>(hw.u16.data(), hw.u16.size() * 2);
+            m.head.rows = c.vocab;
+            m.head.cols = H;
+        } else if (hw.dtype == "Q" || hw.dtype == "R") {
+            m.head = L.finish(hw);
         } else {
-            if (m.embed_fmt == 2) throw Unsupported("a tied LM head needs a 16-bit embed_tokens.weight");
-            m.head = m.embed;
-            m.head_fmt = m.embed_fmt;
-            m.tied = true;
+            throw Unsupported("LM lm_head.weight has dtype " + hw.dtype + " (16-bit BF16 / F16 only)");
         }
     }
     m.act = m.layers.empty() ? ActType::BF16 : m.layers[0].w_qkv.act();

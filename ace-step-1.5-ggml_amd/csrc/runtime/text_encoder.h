@@ -22,14 +22,15 @@ struct TextConfig {
 struct TextModel {
     TextConfig cfg;
     void* embed = nullptr;  // [vocab][hidden]: bf16 / fp16 bits as stored, or f32 values (F32 or quantized)
-    int embed_fmt = 0;      // launch_embed_rows fmt: 0 bf16, 1 fp16, 2 f32
+    int embed_fmt = 0;      // launch_embed_rows fmt: 0 bf16, 1 fp16, 2 f32; 3 (LM only): block planes in embed_q, embed null
+    DevWeight embed_q;      // embed_fmt 3: the table in Q8_0 / Q4_K / Q6_K planes (the gather reads rows of the planes)
     float* norm = nullptr;  // [hidden]
     std::vector<DevLayer> layers;
     ActType act = ActType::BF16;
     int qtype = 0;
-    // causal-LM head (TextLoadOptions::lm_head): [vocab][hidden] 16-bit, lm_head.weight or the tied embed table
-    void* head = nullptr;
-    int head_fmt = 0;  // 0 bf16, 1 fp16
+    // causal-LM head (TextLoadOptions::lm_head): [vocab][hidden], lm_head.weight or the tied embed table, in any form
+    // Loader::finish gives a matrix (dense 16-bit, block planes, bf16 image); tied: the table's own allocation
+    DevWeight head;
     bool tied = false;
     std::vector<void*> allocs;
     size_t weight_bytes = 0;
@@ -41,7 +42,10 @@ struct TextModel {
 struct TextLoadOptions {
     bool model_prefix = false;   // also accept the HF causal-LM names "model.<tensor>"
     bool lm_head = false;        // resolve the head: lm_head.weight when the file has it, else the tied embed table
-    bool dense16_only = false;   // refuse GGUF files, ACE_GGML_QWEN_WEIGHT_QTYPE and a non-16-bit embed table (Unsupported)
+    // ace_mi_load_lm's checkpoint rules: a GGUF comes from the path, dir/model.gguf or ACE_GGML_LM_GGUF alone (the
+    // text encoder's keys are not consulted) and keeps its types; a safetensors checkpoint must be 16-bit (no
+    // ACE_GGML_QWEN_WEIGHT_QTYPE, no F32 embed table: Unsupported); a plane-typed table stays in planes
+    bool lm_checkpoint = false;
 };
 
 // Throws std::runtime_error (the ABI reports ACE_GGML_ERR_IO like load_qwen_dir, acestep_ggml.cpp:238-244).

@@ -116,6 +116,18 @@ ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_skinny(int32_t act_type, int32_t e
 /* Embedding rows: out [n][H] f32 = table [vocab][H] at ids [n] clamped into the table. */
 ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_embed(int32_t fmt, int32_t n, int32_t vocab, int32_t H,
                                                     const uint16_t* table, const int32_t* ids, float* out);
+/* The same two on a weight in ggml block planes (csrc/kernels/lm_decode_q.hip).  qtype: ace_mi_quantize's
+ * ids 1 Q8_0 / 2 Q4_K / 3 Q6_K; blocks: ggml block bytes [w_rows][row bytes] (w_rows >= N: rows past N are uploaded and must not be
+ * read), re-laid out into the loader's planes here; x bf16.  *chain (may be NULL) receives the longest f32 addition
+ * chain behind one output for this type and K, the c - 2 of the tests' bound. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_skinny_q(int32_t qtype, int32_t epi, int32_t B, int32_t N, int32_t w_rows,
+                                                       int32_t K, int32_t ldx, int32_t ldy, const uint16_t* x,
+                                                       const uint8_t* blocks, float* y_f32, uint16_t* y_u16,
+                                                       int32_t* chain);
+/* Embedding rows from the planes: out [n][H] f32 = the f32 dequant (ggml get_rows) of blocks [vocab][row bytes] at
+ * ids [n] clamped into the table. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_embed_q(int32_t qtype, int32_t n, int32_t vocab, int32_t H,
+                                                      const uint8_t* blocks, const int32_t* ids, float* out);
 /* Decode step's q/k norm + RoPE + cache append at slot pos: qkv [B][ld] f32, q_norm / k_norm [128], rope_cos / rope_sin
  * [capacity][64], mask_new [B] or NULL; q_out [B][hq][128] f32; k_cache / v_cache [B][hkv][capacity][128] fp16 and
  * key_mask [B][capacity] (one layer) are in-out. */

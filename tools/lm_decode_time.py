@@ -11,7 +11,12 @@ Qwen3-1.7B shapes (the models' public config.json), beside two numbers from the 
 The 5 Hz LM extends the stock vocabulary with audio-code tokens: --vocab sets the size (default: stock Qwen3, 151936).
 Each step is timed on its own with a pair of events after warm-up steps; the table gives median, min and max.
 
-  python tools/lm_decode_time.py --models 0.6b,1.7b --steps 30 --warmup 5 [--no-torch] [--json out.json]"""
+--gguf Q8_0,Q4_K,Q6_K adds, per type, the same engine measurement on a GGUF checkpoint of that type at the same shape
+(every 2-D tensor in random valid blocks of the type, norms F32, tied head: the step then runs kernels/lm_decode_q.hip
+on the block planes, 1.125 / 0.75 / 1.25 bytes per weight); torch eager is measured for the dense checkpoint only.
+
+  python tools/lm_decode_time.py --models 0.6b,1.7b --steps 30 --warmup 5 [--gguf Q8_0,Q4_K,Q6_K] [--no-torch]
+                                 [--json out.json]"""
 import argparse
 import json
 import os
@@ -34,11 +39,14 @@ SHAPES = {  # Qwen/Qwen3-0.6B and Qwen/Qwen3-1.7B config.json
 HBM_PEAK, HBM_MEASURED = 8.0e12, 6.3e12
 
 
-def step_bytes(cfg, B, cache_len):
+PLANE_BYTES = {"Q8_0": 1.125, "Q4_K": 0.75, "Q6_K": 1.25}   # resident (and read) bytes per weight of the block planes
+
+
+def step_bytes(cfg, B, cache_len, bytes_per_weight=2.0):
     H, I, D = cfg["hidden_size"], cfg["intermediate_size"], cfg["head_dim"]
     qd, kd = cfg["num_attention_heads"] * D, cfg["num_key_value_heads"] * D
-    layer = ((qd + 2 * kd) * H + H * qd + 2 * I * H + H * I) * 2
-    weights = cfg["num_hidden_layers"] * layer + cfg["vocab_size"] * H * 2
+    layer = (qd + 2 * kd) * H + H * qd + 2 * I * H + H * I
+    weights = int((cfg["num_hidden_layers"] * layer + cfg["vocab_size"] * H) * bytes_per_weight)
     cache = B * cache_len * cfg["num_hidden_layers"] * 2 * kd * 2          # K and V, fp16
     return weights, cache
 
@@ -118,6 +126,7 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--gguf", default="", help="comma-separated block types (Q8_0, Q4_K, Q6_K) to time as GGUF files")
     ap.add_argument("--json", default=None)
     a = ap.parse_args()
     Bs, lens = [int(x) for x in a.batch.split(",")], [int(x) for x in a.cache.split(",")]
@@ -131,19 +140,26 @@ def main():
             _write(d, cfg)
             eng = engine_times(d, cfg, Bs, lens, a.warmup, a.steps)
             ref = {} if a.no_torch else torch_times(d, dict(cfg, tie_word_embeddings=True), Bs, lens, a.warmup, a.steps)
-        for B in Bs:
-            for L in lens:
-                w, c = step_bytes(cfg, B, L)
-                e, t = eng[(B, L)], ref.get((B, L))
-                row = dict(model=name, B=B, cache=L, engine_ms=e, weight_bytes=w, cache_bytes=c,
-                           roofline_peak_ms=(w + c) / HBM_PEAK * 1e3, roofline_measured_ms=(w + c) / HBM_MEASURED * 1e3,
-                           torch_ms=t)
-                rows.append(row)
-                ts = f"{t['median']:.3f} ({t['min']:.3f}-{t['max']:.3f})" if t else "-"
-                ratio = f"{t['median'] / e['median']:.2f}x" if t else "-"
-                print(f"| {name} | {B} | {L} | {e['median']:.3f} ({e['min']:.3f}-{e['max']:.3f}) | "
-                      f"{(w + c) / 1e6:.0f} ({w / 1e6:.0f} + {c / 1e6:.0f}) | {row['roofline_peak_ms']:.3f} | "
-                      f"{row['roofline_measured_ms']:.3f} | {ts} | {ratio} |", flush=True)
+        runs = [(name, 2.0, eng, ref)]
+        for qt in [q for q in a.gguf.split(",") if q]:
+            with tempfile.TemporaryDirectory(prefix="acemi_lmtime_gguf_") as d:
+                _write_gguf(d, cfg, qt)
+                runs.append((f"{name} {qt}", PLANE_BYTES[qt], engine_times(d, cfg, Bs, lens, a.warmup, a.steps), {}))
+        for label, bpw, eng, ref in runs:
+            for B in Bs:
+                for L in lens:
+                    w, c = step_bytes(cfg, B, L, bpw)
+                    e, t = eng[(B, L)], ref.get((B, L))
+                    name = label
+                    row = dict(model=name, B=B, cache=L, engine_ms=e, weight_bytes=w, cache_bytes=c,
+                               roofline_peak_ms=(w + c) / HBM_PEAK * 1e3, roofline_measured_ms=(w + c) / HBM_MEASURED * 1e3,
+                               torch_ms=t)
+                    rows.append(row)
+                    ts = f"{t['median']:.3f} ({t['min']:.3f}-{t['max']:.3f})" if t else "-"
+                    ratio = f"{t['median'] / e['median']:.2f}x" if t else "-"
+                    print(f"| {name} | {B} | {L} | {e['median']:.3f} ({e['min']:.3f}-{e['max']:.3f}) | "
+                          f"{(w + c) / 1e6:.0f} ({w / 1e6:.0f} + {c / 1e6:.0f}) | {row['roofline_peak_ms']:.3f} | "
+                          f"{row['roofline_measured_ms']:.3f} | {ts} | {ratio} |", flush=True)
     if a.json:
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
@@ -155,6 +171,24 @@ def _write(d, cfg):
     from acestep_mi355x.synthetic import lm_tensor_specs, write_checkpoint
     cfg = dict(cfg, architectures=["Qwen3ForCausalLM"], tie_word_embeddings=True)
     return write_checkpoint(d, cfg, seed=1, dtype="BF16", backend="torch", specs=lm_tensor_specs(cfg, tied=True))
+
+
+def _write_gguf(d, cfg, qtype):
+    """config.json + model.gguf: every 2-D tensor in random valid blocks of qtype (synthetic.random_blocks: timing needs
+    bytes, not values), norms F32 ones, no lm_head.weight (tied)."""
+    import numpy as np
+    from acestep_mi355x.synthetic import lm_tensor_specs, random_blocks, write_gguf_tensors
+    cfg = dict(cfg, architectures=["Qwen3ForCausalLM"], tie_word_embeddings=True)
+    with open(os.path.join(d, "config.json"), "w") as f:
+        json.dump(cfg, f)
+    rng = np.random.default_rng(1)
+    tensors = {}
+    for name, shape, kind in lm_tensor_specs(cfg, tied=True):
+        if kind == "norm":
+            tensors[name] = (shape, "F32", np.ones(shape, "<f4").tobytes())
+        else:
+            tensors[name] = (shape, qtype, random_blocks(qtype, shape[0], shape[1], rng).tobytes())
+    return write_gguf_tensors(os.path.join(d, "model.gguf"), tensors)
 
 
 if __name__ == "__main__":
