@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "ace_ggml_text_encoder_forward_layers", "ace_ggml_generate_audio_simple", "ace_ggml_generate_audio_style_lyric_simple",
     "ace_ggml_generate_audio_style_lyric_timbre_simple", "ace_mi_reference_noise",
     "ace_mi_load_lm", "ace_mi_lm_get_info", "ace_mi_lm_begin", "ace_mi_lm_forward", "ace_mi_lm_reset",
+    "ace_mi_lm_select", "ace_mi_lm_generate",
 )
 
 # Every symbol declared in include/acestep_mi355x_selftest.h: the TEST library (libacestep_mi355x_selftest.so = the
@@ -54,7 +55,7 @@ SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_ben
                     "ace_mi_gemm_resolve", "ace_mi_gemm_variant_row", "ace_mi_gemm_variant_arg_ok",
                     "ace_mi_kernel_lm_skinny", "ace_mi_kernel_lm_embed", "ace_mi_kernel_lm_qkv_post",
                     "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention", "ace_mi_kernel_lm_skinny_q",
-                    "ace_mi_kernel_lm_embed_q")
+                    "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_select")
 
 # qtype codes of ace_mi_quantize & co. (names as parse_quant_type, acestep_dit_model.cpp:27-37)
 QTYPES = {"q8_0": 1, "q4_k": 2, "q6_k": 3,
@@ -97,6 +98,27 @@ class AceMiLmInfo(ctypes.Structure):
         "vocab_size", "hidden_size", "num_layers", "num_heads", "num_kv_heads", "head_dim", "max_positions", "tied",
         "act_type", "batch", "capacity", "cache_len")] + [("weight_bytes", ctypes.c_int64),
                                                           ("cache_bytes", ctypes.c_int64)]
+
+
+class AceMiLmSampleParams(ctypes.Structure):
+    """ace_mi_lm_sample_params (include/acestep_mi355x.h)."""
+    _fields_ = [("cfg_scale", ctypes.c_float), ("pre_temperature", ctypes.c_float), ("repetition_penalty", ctypes.c_float),
+                ("top_k", ctypes.c_int32), ("top_p", ctypes.c_float), ("temperature", ctypes.c_float),
+                ("d_allowed", ctypes.c_void_p), ("n_allowed", ctypes.c_int32), ("stop_id", ctypes.c_int32),
+                ("min_tokens", ctypes.c_int32), ("seed", ctypes.c_uint64)]
+
+
+class AceMiKernelLmSelectArgs(ctypes.Structure):
+    """ace_mi_kernel_lm_select_args (include/acestep_mi355x_selftest.h)."""
+    _fields_ = [("B", ctypes.c_int32), ("vocab", ctypes.c_int32), ("ld_logits", ctypes.c_int32),
+                ("cfg_scale", ctypes.c_float), ("pre_temperature", ctypes.c_float), ("repetition_penalty", ctypes.c_float),
+                ("top_k", ctypes.c_int32), ("top_p", ctypes.c_float), ("temperature", ctypes.c_float),
+                ("n_allowed", ctypes.c_int32), ("stop_id", ctypes.c_int32), ("block_stop", ctypes.c_int32),
+                ("force_stop", ctypes.c_int32), ("n_emitted", ctypes.c_int32), ("ld_seen", ctypes.c_int32),
+                ("token_stride", ctypes.c_int32), ("ld_processed", ctypes.c_int32),
+                ("logits", ctypes.c_void_p), ("allowed", ctypes.c_void_p), ("uniform", ctypes.c_void_p),
+                ("seen", ctypes.c_void_p), ("tokens", ctypes.c_void_p), ("next_ids", ctypes.c_void_p),
+                ("done", ctypes.c_void_p), ("processed", ctypes.c_void_p), ("chains", ctypes.c_void_p)]
 
 
 class AceMiBlockSeg(ctypes.Structure):
@@ -242,6 +264,11 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.ace_mi_lm_forward.restype = ctypes.c_int
         lib.ace_mi_lm_reset.argtypes = [vp]
         lib.ace_mi_lm_reset.restype = ctypes.c_int
+        pp = ctypes.POINTER(AceMiLmSampleParams)
+        lib.ace_mi_lm_select.argtypes = [vp, pp, vp, vp, vp, i32, i32, vp, vp]
+        lib.ace_mi_lm_select.restype = ctypes.c_int
+        lib.ace_mi_lm_generate.argtypes = [vp, pp, vp, i32, vp, vp, vp, ip, vp]
+        lib.ace_mi_lm_generate.restype = ctypes.c_int
     if path is None:
         _LIB = lib
     return lib
@@ -496,6 +523,85 @@ class GGMLCAPIBridge:
             self.lm_forward_device(ids.data_ptr(), am.data_ptr() if am is not None else 0, ids.shape[1],
                                    out.data_ptr(), stream)
         return out
+
+    def _lm_sample_params(self, dev, allowed_ids=None, stop_id=-1, min_tokens=0, cfg_scale=1.0, pre_temperature=0.0,
+                          temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0):
+        """(ace_mi_lm_sample_params, the device tensor it points into): allowed_ids = ascending ids or None."""
+        import torch
+        allowed = None
+        if allowed_ids is not None:
+            allowed = torch.as_tensor(allowed_ids).detach().to(device=dev, dtype=torch.int32).contiguous().reshape(-1)
+        p = AceMiLmSampleParams(
+            cfg_scale=float(cfg_scale), pre_temperature=float(pre_temperature or 0.0),
+            repetition_penalty=float(repetition_penalty), top_k=int(top_k or 0),
+            top_p=float(top_p if top_p is not None else 1.0), temperature=float(temperature),
+            d_allowed=allowed.data_ptr() if allowed is not None and allowed.numel() else None,
+            n_allowed=int(allowed.numel()) if allowed is not None else 0,
+            stop_id=-1 if stop_id is None else int(stop_id), min_tokens=int(min_tokens), seed=int(seed) & (2 ** 64 - 1))
+        if allowed is not None and allowed.numel() == 0:
+            p.d_allowed = ctypes.c_void_p(1).value  # an empty list stays a list: the entry refuses n_allowed < 1
+        return p, allowed
+
+    def lm_select(self, logits, uniforms=None, seen=None, n_emitted: int = 0, force_stop: bool = False, **params):
+        """One token per sampled sequence from `logits` [B, vocab] (f32 tensor on the engine's device, as lm_forward
+        returns them): ace_mi_lm_select with the keyword parameters of _lm_sample_params.  uniforms: f32 [S] (needed
+        when temperature > 0); seen: uint8 [S, vocab] map, updated in place.  Returns int32 [S], in stream order on
+        torch's current stream (the stream rules of lm_forward)."""
+        import torch
+        from .hook import _OrderedCall
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 2:
+            raise ValueError("lm_select: logits must be a contiguous f32 [B, vocab] tensor")
+        dev = logits.device
+        p, keep = self._lm_sample_params(dev, **params)
+        S = logits.shape[0] // 2 if p.cfg_scale > 1.0 else logits.shape[0]
+        u = None
+        if uniforms is not None:
+            u = uniforms.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if u.numel() != S and not (p.cfg_scale > 1.0 and logits.shape[0] % 2):  # an odd pair batch: the entry refuses
+                raise ValueError("lm_select: uniforms must hold one value per sampled sequence")
+        if seen is not None and (seen.dtype != torch.uint8 or not seen.is_contiguous() or seen.device != dev
+                                 or tuple(seen.shape) != (S, logits.shape[1])):
+            raise ValueError("lm_select: seen must be a contiguous uint8 [S, vocab] tensor on the logits' device")
+        out = torch.empty((max(S, 1),), dtype=torch.int32, device=dev)
+        with _OrderedCall(self, dev) as stream:
+            st = self.lib.ace_mi_lm_select(self.ctx, ctypes.byref(p), logits.data_ptr(),
+                                           u.data_ptr() if u is not None else None,
+                                           seen.data_ptr() if seen is not None else None, int(n_emitted),
+                                           1 if force_stop else 0, out.data_ptr(), stream or None)
+        self._ensure_ok(st, "ace_mi_lm_select")
+        del keep
+        return out[:S]
+
+    def lm_generate(self, logits, n_max: int, uniforms=None, seen=None, **params):
+        """The engine-side decode loop (ace_mi_lm_generate) on the live cache: `logits` [B, vocab] f32 are those of the
+        last lm_forward and are overwritten.  uniforms: f32 [n_max, S] or None (the engine then draws them from
+        params' seed).  Returns (tokens int32 [S, n_max], n_out); the call returns once the loop has run."""
+        import torch
+        from .hook import _OrderedCall
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 2:
+            raise ValueError("lm_generate: logits must be a contiguous f32 [B, vocab] tensor")
+        dev = logits.device
+        p, keep = self._lm_sample_params(dev, **params)
+        S = logits.shape[0] // 2 if p.cfg_scale > 1.0 else logits.shape[0]
+        n_max = int(n_max)
+        u = None
+        if uniforms is not None:
+            u = uniforms.detach().to(device=dev, dtype=torch.float32).contiguous()
+            if u.numel() != max(n_max, 0) * S:
+                raise ValueError("lm_generate: uniforms must be [n_max, S]")
+        if seen is not None and (seen.dtype != torch.uint8 or not seen.is_contiguous() or seen.device != dev
+                                 or tuple(seen.shape) != (S, logits.shape[1])):
+            raise ValueError("lm_generate: seen must be a contiguous uint8 [S, vocab] tensor on the logits' device")
+        out = torch.zeros((max(S, 1), max(n_max, 1)), dtype=torch.int32, device=dev)
+        n_out = ctypes.c_int32(0)
+        with _OrderedCall(self, dev) as stream:
+            st = self.lib.ace_mi_lm_generate(self.ctx, ctypes.byref(p), logits.data_ptr(), n_max,
+                                             u.data_ptr() if u is not None else None,
+                                             seen.data_ptr() if seen is not None else None, out.data_ptr(),
+                                             ctypes.byref(n_out), stream or None)
+        self._ensure_ok(st, "ace_mi_lm_generate")
+        del keep
+        return out[:S], int(n_out.value)
 
     # reference GGMLCAPIBridge names (scripts/run_non_ggml_real_case.py:255-281)
     def text_forward_full(self, token_ids, hidden_dim: int) -> np.ndarray:
@@ -937,7 +1043,8 @@ def _bind_lm_kernels(lib):
     u8p = ctypes.POINTER(ctypes.c_uint8)
     lib.ace_mi_kernel_lm_skinny_q.argtypes = [i32] * 8 + [u16p, u8p, fp, u16p, ip]
     lib.ace_mi_kernel_lm_embed_q.argtypes = [i32] * 4 + [u8p, ip, fp]
-    for name in ("skinny", "embed", "qkv_post", "prefill_kv", "attention", "skinny_q", "embed_q"):
+    lib.ace_mi_kernel_lm_select.argtypes = [ctypes.POINTER(AceMiKernelLmSelectArgs)]
+    for name in ("skinny", "embed", "qkv_post", "prefill_kv", "attention", "skinny_q", "embed_q", "select"):
         getattr(lib, "ace_mi_kernel_lm_" + name).restype = ctypes.c_int
     return lib
 
@@ -1076,6 +1183,44 @@ def kernel_lm_attention(q: np.ndarray, k_cache: np.ndarray, v_cache: np.ndarray,
                                         _u16ptr(vc), _iptr(km), _u16ptr(out))
     _lm_status("attention", st)
     return out
+
+
+def kernel_lm_select(logits: np.ndarray, cfg_scale=1.0, pre_temperature=0.0, repetition_penalty=1.0, top_k=0, top_p=1.0,
+                     temperature=1.0, allowed=None, stop_id=-1, block_stop=False, force_stop=False, n_emitted=0,
+                     uniform=None, seen=None, tokens0=None, token_stride=1, next_ids0=None, done0=None, processed0=None,
+                     vocab=None, lib=None) -> dict:
+    """launch_lm_select on host arrays: logits [B][ld] f32 whose first `vocab` columns count (default: all).  seen
+    [S][ld_seen] uint8, tokens0 [S * token_stride] int32, next_ids0 [B], done0 [1 + S] and processed0 [S][ld_processed]
+    give the initial content of the in-out buffers (None = not passed, but for tokens0).  Returns a dict of the buffers
+    after the launch: tokens, seen, next_ids, done, processed, chains."""
+    lib = _lm_lib(lib)
+    x = np.ascontiguousarray(logits, dtype=np.float32)
+    B, ld = x.shape
+    vocab = ld if vocab is None else int(vocab)
+    S = B // 2 if cfg_scale > 1.0 else B
+    al = None if allowed is None else np.ascontiguousarray(allowed, dtype=np.int32)
+    u = None if uniform is None else np.ascontiguousarray(uniform, dtype=np.float32)
+    tok = (np.full((max(S, 1) * token_stride,), -7, np.int32) if tokens0 is None
+           else np.array(tokens0, dtype=np.int32, order="C", copy=True))
+    sn = None if seen is None else np.array(seen, dtype=np.uint8, order="C", copy=True)
+    nx = None if next_ids0 is None else np.array(next_ids0, dtype=np.int32, order="C", copy=True)
+    dn = None if done0 is None else np.array(done0, dtype=np.int32, order="C", copy=True)
+    pr = None if processed0 is None else np.array(processed0, dtype=np.float32, order="C", copy=True)
+    chains = np.zeros(3, np.int32)
+
+    def ptr(a):
+        return None if a is None else a.ctypes.data
+
+    g = AceMiKernelLmSelectArgs(
+        B=B, vocab=vocab, ld_logits=ld, cfg_scale=cfg_scale, pre_temperature=pre_temperature,
+        repetition_penalty=repetition_penalty, top_k=int(top_k), top_p=top_p, temperature=temperature,
+        n_allowed=0 if al is None else int(al.shape[0]), stop_id=int(stop_id), block_stop=int(bool(block_stop)),
+        force_stop=int(bool(force_stop)), n_emitted=int(n_emitted), ld_seen=0 if sn is None else sn.shape[1],
+        token_stride=int(token_stride), ld_processed=0 if pr is None else pr.shape[1], logits=ptr(x), allowed=ptr(al),
+        uniform=ptr(u), seen=ptr(sn), tokens=ptr(tok), next_ids=ptr(nx), done=ptr(dn), processed=ptr(pr),
+        chains=ptr(chains))
+    _lm_status("select", lib.ace_mi_kernel_lm_select(ctypes.byref(g)))
+    return {"tokens": tok, "seen": sn, "next_ids": nx, "done": dn, "processed": pr, "chains": chains}
 
 
 def kernel_gemm_q(a_bits: np.ndarray, w_blocks: np.ndarray, qtype: str, epi: int = 0, variant: int = -1,

@@ -327,7 +327,8 @@ class EngineCausalLM:
     """`llm_handler.llm` drop-in for the reference's `pt` backend (acestep/llm_inference.py:345-367, :2259-2471): the
     two custom loops only ever call `model(input_ids=..., attention_mask=..., past_key_values=..., use_cache=...)` and
     read `.logits[:, -1, :]` and `.past_key_values`.  The engine supplies the logits (ace_mi_lm_forward); the
-    constrained-decoding FSM, CFG mixing and sampling stay in the reference's Python."""
+    constrained-decoding FSM, CFG mixing and sampling stay in the reference's Python, unless install_lm_backend was
+    given device_codes=True: then the audio-code phase runs in the engine (generate_codes, ace_mi_lm_generate)."""
 
     def __init__(self, bridge, device=None, max_new_tokens: int = 4096):
         import torch
@@ -371,20 +372,182 @@ class EngineCausalLM:
             mask = attention_mask[:, attention_mask.shape[-1] - n:]
         logits = self.bridge.lm_forward(input_ids, mask)
         self._live.length += n
+        self._last_logits = logits
         return _LmOutput(logits[:, None, :], self._live)
 
     forward = __call__
 
+    def generate_codes(self, n_codes: int, allowed_ids, eos_id: int, cfg_scale: float = 1.0, codes_temperature=None,
+                       temperature: float = 1.0, top_k=None, top_p=None, repetition_penalty: float = 1.0,
+                       prompt_ids=None, seed: int = 0, uniforms=None):
+        """n_codes tokens of the audio-code phase in one engine call (bridge.lm_generate) on the live cache, starting
+        from the logits of the newest forward: candidates = allowed_ids (ascending) without eos_id, which the duration
+        constraint blocks for all n_codes tokens; the caller appends EOS.  cfg_scale > 1 mixes the two halves of the
+        batch.  A repetition penalty needs prompt_ids [S, n]: every id the sampled sequences hold so far.  uniforms
+        [n_codes, S] replace the engine's own draws from `seed`.  Returns int32 [S, n_codes]; the cache then holds
+        n_codes - 1 more tokens, the last one is not fed back."""
+        import torch
+        if self._live is None or getattr(self, "_last_logits", None) is None:
+            raise ValueError("generate_codes: no live cache; run the prompt through the model first")
+        logits = self._last_logits
+        S = logits.shape[0] // 2 if cfg_scale > 1.0 else logits.shape[0]
+        seen = None
+        if repetition_penalty != 1.0:
+            if prompt_ids is None:
+                raise ValueError("generate_codes: a repetition penalty needs prompt_ids")
+            seen = torch.zeros((S, logits.shape[1]), dtype=torch.uint8, device=logits.device)
+            seen.scatter_(1, prompt_ids[:S].to(device=logits.device, dtype=torch.long), 1)
+        pre = 0.0
+        if codes_temperature is not None:
+            pre = float(codes_temperature) if codes_temperature > 0 else 1e-6
+        tokens, n = self.bridge.lm_generate(
+            logits, int(n_codes), uniforms=uniforms, seen=seen, allowed_ids=allowed_ids, stop_id=eos_id,
+            min_tokens=int(n_codes), cfg_scale=cfg_scale, pre_temperature=pre, temperature=temperature, top_k=top_k,
+            top_p=top_p, repetition_penalty=repetition_penalty, seed=seed)
+        self._live.length += int(n_codes) - 1
+        self._last_logits = None  # scratch of the loop now
+        return tokens[:, :n]
 
-def install_lm_backend(llm_handler: Any, bridge, max_new_tokens: int = 4096) -> None:
+
+def _state_name(proc) -> str:
+    st = getattr(proc, "state", None)
+    return getattr(st, "name", str(st))
+
+
+def _codes_handoff(proc):
+    """(allowed ids, eos id, codes left) when the constrained processor is in its audio-code phase with everything the
+    engine loop needs, else None."""
+    import torch
+    if proc is None or not getattr(proc, "enabled", True) or _state_name(proc) != "CODES_GENERATION":
+        return None  # a disabled processor applies no mask and counts nothing: nothing to hand over
+    target, eos = getattr(proc, "target_codes", None), getattr(proc, "eos_token_id", None)
+    mask = getattr(proc, "non_audio_code_mask", None)
+    if target is None or eos is None or mask is None:
+        return None
+    left = int(target) - int(getattr(proc, "codes_count", 0))
+    if left < 1:
+        return None
+    allowed = torch.nonzero(torch.isfinite(mask.reshape(-1).float())).reshape(-1)
+    allowed = allowed[allowed != int(eos)]
+    if allowed.numel() < 1:
+        return None
+    return allowed, int(eos), left
+
+
+def _penalise(logits, ids, penalty: float):
+    """HF RepetitionPenaltyLogitsProcessor on [S, vocab] logits for the ids [S, n] seen so far."""
+    import torch
+    score = torch.gather(logits, 1, ids)
+    score = torch.where(score < 0, score * penalty, score / penalty)
+    return logits.scatter(1, ids, score)
+
+
+def _engine_loop(handler, ids, mask, max_new_tokens, temperature, cfg_scale, top_k, top_p, repetition_penalty,
+                 pad_token_id, streamer, proc):
+    """The handler's token loop with the audio-code phase handed to the engine.  cfg_scale None: every row is sampled;
+    otherwise the first half of the batch is conditional, the second unconditional, and both get the sampled token."""
+    import torch
+    model, device = handler.llm, handler.device
+    S = ids.shape[0] // 2 if cfg_scale is not None else ids.shape[0]
+    rep = 2 if cfg_scale is not None else 1
+    out = ids.clone()
+    am = mask.clone() if mask is not None else torch.ones_like(ids)
+    eos = getattr(getattr(handler, "llm_tokenizer", None), "eos_token_id", None)
+    if eos is None:
+        eos = pad_token_id
+    extra = handler._build_logits_processor(repetition_penalty) if hasattr(handler, "_build_logits_processor") else None
+    past = None
+    step = 0
+    with torch.inference_mode():
+        while step < max_new_tokens:
+            res = model(input_ids=out if past is None else out[:, -1:], attention_mask=am, past_key_values=past,
+                        use_cache=True)
+            past = res.past_key_values
+            hand = None
+            if streamer is None and isinstance(model, EngineCausalLM) and (cfg_scale is None or cfg_scale > 1.0):
+                hand = _codes_handoff(proc)
+            if hand is not None:
+                allowed, eos_id, left = hand
+                n = min(left, max_new_tokens - step)
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # torch's seeded CPU generator picks the stream
+                toks = model.generate_codes(
+                    n, allowed, eos_id, cfg_scale=cfg_scale if cfg_scale is not None else 1.0,
+                    codes_temperature=getattr(proc, "codes_temperature", None), temperature=temperature, top_k=top_k,
+                    top_p=top_p, repetition_penalty=repetition_penalty, prompt_ids=out[:S], seed=seed)
+                toks = toks.to(device=out.device, dtype=out.dtype)
+                out = torch.cat([out, toks.repeat(rep, 1)], dim=1)
+                proc.codes_count = int(getattr(proc, "codes_count", 0)) + n
+                step += n
+                if n == left and step < max_new_tokens:  # the forced EOS of the duration constraint
+                    out = torch.cat([out, torch.full((out.shape[0], 1), eos_id, dtype=out.dtype, device=out.device)], dim=1)
+                    st = getattr(proc, "state", None)
+                    proc.state = type(st)["COMPLETED"] if hasattr(type(st), "__members__") else "COMPLETED"
+                break
+            logits = res.logits[:, -1, :]
+            if cfg_scale is not None:
+                logits = logits[S:].float() + cfg_scale * (logits[:S].float() - logits[S:].float())
+            cur = out[:S]
+            if proc is not None:
+                logits = proc(cur, logits)
+            if extra is not None:
+                for f in extra:
+                    logits = f(cur, logits)
+            elif repetition_penalty != 1.0:
+                logits = _penalise(logits, cur, repetition_penalty)
+            logits = handler._apply_top_k_filter(logits, top_k)
+            logits = handler._apply_top_p_filter(logits, top_p)
+            nxt = handler._sample_tokens(logits, temperature)
+            if proc is not None:
+                for b in range(nxt.shape[0]):
+                    proc.update_state(nxt[b].item())
+            stop = bool(torch.any(nxt == eos))
+            if pad_token_id is not None and pad_token_id != eos:
+                stop = stop or bool(torch.any(nxt == pad_token_id))
+            col = nxt.unsqueeze(1)
+            out = torch.cat([out, col.repeat(rep, 1)], dim=1)
+            am = torch.cat([am, torch.ones((am.shape[0], 1), device=am.device, dtype=am.dtype)], dim=1)
+            if streamer is not None:
+                streamer.put(col)
+            step += 1
+            if stop:
+                break
+    if streamer is not None:
+        streamer.end()
+    return out
+
+
+def install_lm_backend(llm_handler: Any, bridge, max_new_tokens: int = 4096, device_codes: bool = False) -> None:
     """Point the reference LLM handler's `pt` backend at the engine: `llm_handler.llm` becomes an EngineCausalLM over
-    the LM that `bridge.load_lm` loaded (needs no `transformers`)."""
+    the LM that `bridge.load_lm` loaded (needs no `transformers`).
+
+    device_codes=True also replaces the handler's two loops (_generate_with_constrained_decoding,
+    _generate_with_cfg_custom; same signatures and return values) with engine-aware ones: token by token they do what
+    the reference loops do (engine logits, the handler's own filters and sampler, the processor's __call__ and
+    update_state) until the constrained processor is in CODES_GENERATION with target_codes, eos_token_id and a
+    non_audio_code_mask; everything left then runs in one generate_codes call, codes_count and the COMPLETED state are
+    written back and EOS is appended.  A streamer, a processor that is disabled or has no target or mask, no
+    processor, or a cfg_scale <= 1 in the CFG loop keep the per-token path.  Off by default: the engine draws from its own seeded uniforms, not torch.multinomial, so the same
+    torch seed gives other (equally distributed) codes."""
     device = getattr(llm_handler, "device", None)
     if device is None or str(device) in ("auto", "cpu"):
         device = "cuda"
     llm_handler.llm = EngineCausalLM(bridge, device=device, max_new_tokens=max_new_tokens)
     llm_handler.llm_backend = "pt"
     setattr(llm_handler, "_ggml_lm_backend", "mi355x-capi")
+    if device_codes:
+        def constrained_mi355x(self, input_ids, attention_mask, max_new_tokens, temperature, top_k, top_p,
+                               repetition_penalty, pad_token_id, streamer, constrained_processor=None):
+            return _engine_loop(self, input_ids, attention_mask, max_new_tokens, temperature, None, top_k, top_p,
+                                repetition_penalty, pad_token_id, streamer, constrained_processor)
+
+        def cfg_mi355x(self, batch_input_ids, batch_attention_mask, max_new_tokens, temperature, cfg_scale, top_k, top_p,
+                       repetition_penalty, pad_token_id, streamer, constrained_processor=None):
+            return _engine_loop(self, batch_input_ids, batch_attention_mask, max_new_tokens, temperature, float(cfg_scale),
+                                top_k, top_p, repetition_penalty, pad_token_id, streamer, constrained_processor)
+
+        llm_handler._generate_with_constrained_decoding = types.MethodType(constrained_mi355x, llm_handler)
+        llm_handler._generate_with_cfg_custom = types.MethodType(cfg_mi355x, llm_handler)
+        setattr(llm_handler, "_ggml_lm_device_codes", True)
 
 
 def install_text_encoder_backend(dit_handler: Any, bridge) -> None:

@@ -422,6 +422,48 @@ size_t lm_attn_part_floats(int B, int hq, int nk);
 // >= nk are not read, and a sequence whose keys are all masked gets exactly +0 in every output word of either type.
 void launch_lm_attention(ActType out_t, const LmAttnArgs& a, int B, int hq, hipStream_t s);
 
+// ------------------------------------------------------------ LM token selection (kernels/lm_sample.hip)
+// One token per sampled sequence from the f32 logits of a forward: CFG mix, candidate set, phase temperature,
+// repetition penalty, top-k, top-p, then a draw (or the argmax) -- the codes-phase pipeline of the reference's loops.
+// Every step up to the top-p cut is a separately rounded f32 operation (semantics and order: include/acestep_mi355x.h,
+// ace_mi_lm_select); the thresholds come from selection, never from a sort; one launch; bit-identical between runs.
+struct LmSelectArgs {
+    const float* logits = nullptr;  // [B][ld_logits]; S sampled sequences: cfg_scale > 1 -> S = B/2, row s cond, s+S uncond
+    int64_t ld_logits = 0;
+    int vocab = 0;
+    int S = 0;
+    float cfg_scale = 1.f;           // > 1: mix
+    const int32_t* allowed = nullptr;  // ascending ids, or null = the whole vocabulary
+    int n_allowed = 0;
+    int stop_id = -1;
+    int block_stop = 0;   // the caller's n_emitted < min_tokens
+    int force_stop = 0;   // only stop_id is a candidate
+    int n_emitted = 0;    // index of this token (written to done[0] as n_emitted + 1 on the first stop)
+    float pre_temperature = 0.f;
+    float repetition_penalty = 1.f;
+    uint8_t* seen = nullptr;  // [S][ld_seen] byte map or null; the chosen id's byte is set
+    int64_t ld_seen = 0;
+    int top_k = 0;
+    float top_p = 1.f;
+    float temperature = 1.f;         // <= 0: argmax
+    const float* uniform = nullptr;  // [S] in [0, 1) (temperature > 0)
+    float* work = nullptr;           // lm_select_work_floats() floats of scratch
+    int32_t* tokens = nullptr;       // token of sequence s -> tokens[s * token_stride]
+    int64_t token_stride = 1;
+    int32_t* next_ids = nullptr;  // or null; [B]: rows s and (mixing) s + S
+    int32_t* done = nullptr;      // or null; [1 + S] words: [0] = 1 + index of the first token at which a sequence emitted
+                                  // stop_id (0 = none yet), [1 + s] != 0 = sequence s has stopped and keeps emitting it
+    float* processed = nullptr;   // or null; [S][ld_processed]: the logits as they stand after the top-p cut, -inf
+    int64_t ld_processed = 0;     // where removed
+};
+// candidates of one sequence (the allowed list, else the vocabulary) and the scratch floats launch_lm_select needs
+inline int lm_select_candidates(int vocab, int n_allowed, bool has_list) { return has_list ? n_allowed : vocab; }
+inline size_t lm_select_work_floats(int S, int n_cand) { return (size_t)2 * S * n_cand; }
+void launch_lm_select(const LmSelectArgs& a, hipStream_t s);
+// longest f32 addition chains of launch_lm_select over n_cand candidates, three ints: [0] behind a top-p mass (and
+// behind the top-p total), [1] behind the draw's total, [2] behind a cumulative value of the draw
+void lm_select_chains(int n_cand, int* chains);
+
 // ------------------------------------------------------------ VAE decoder (kernels/vae.hip)
 // Implicit-GEMM conv on fp16 time-major activations.  A row (m, tap) = S[m + tap*dil - pad]
 // (zero row outside [0, T_in)); W [N][taps*Cin] fp16.  up == 1: conv, (m, n) -> (u = m, co = n);

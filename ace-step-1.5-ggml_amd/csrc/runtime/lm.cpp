@@ -14,9 +14,12 @@
 //
 // This file holds both the engine and its C entries, so no other translation unit refers to the launch_lm_* kernels.
 #include <cmath>
+#include <cstdlib>
+#include <random>
 #include <vector>
 
 #include "../kernels/lm_decode_q_host.h"  // empty under hipcc; the host build's launch_lm_skinny_q / launch_lm_embed_q
+#include "../kernels/lm_sample_host.h"    // empty under hipcc; the host build's launch_lm_select
 #include "context.h"
 #include "safetensors.h"
 
@@ -49,11 +52,17 @@ struct DevBuf {
 
 }  // namespace
 
+// tokens between two host reads of the loop's stop word (ace_mi_lm_generate)
+constexpr int LM_STOP_POLL = 16;
+
 class LmEngine {
    public:
     ~LmEngine() {
-        for (DevBuf* b : {&kc_, &vc_, &kmask_, &cos_, &sin_, &x_, &act_, &act2_, &qkv_, &q_, &attn_, &part_, &xn_, &xh_})
+        for (DevBuf* b : {&kc_, &vc_, &kmask_, &cos_, &sin_, &x_, &act_, &act2_, &qkv_, &q_, &attn_, &part_, &xn_, &xh_,
+                          &sel_work_, &sel_next_, &sel_done_, &sel_uni_})
             b->release();
+        if (done_ev_) (void)hipEventDestroy(done_ev_);
+        free_pinned();
     }
     TextModel& model() { return model_; }
     int batch() const { return batch_; }
@@ -130,7 +139,130 @@ class LmEngine {
         len_ += n;
     }
 
+    // The selection arguments shared by select() and generate(); `why` names what is wrong with them, if anything.
+    // first_allowed: the list's first id when it has one entry (the caller read it), else -1.
+    const char* check_sample(const ace_mi_lm_sample_params& p, int n_emitted, bool force_stop, int first_allowed) const {
+        const int vocab = model_.cfg.vocab;
+        if (p.cfg_scale > 1.0f && batch_ % 2 != 0) return "cfg_scale > 1 needs an even batch";
+        if (p.d_allowed && p.n_allowed < 1) return "n_allowed < 1";
+        if (p.stop_id >= vocab) return "stop_id outside the vocabulary";
+        if (force_stop && p.stop_id < 0) return "force_stop without a stop_id";
+        const bool blocked = p.stop_id >= 0 && n_emitted < p.min_tokens && !force_stop;
+        if (blocked && (p.d_allowed ? (p.n_allowed == 1 && first_allowed == p.stop_id) : vocab == 1))
+            return "the candidate set is empty";
+        return nullptr;
+    }
+
+    LmSelectArgs select_args(const ace_mi_lm_sample_params& p, const float* d_logits, uint8_t* d_seen) {
+        const int vocab = model_.cfg.vocab;
+        LmSelectArgs a;
+        a.logits = d_logits;
+        a.ld_logits = vocab;
+        a.vocab = vocab;
+        a.S = p.cfg_scale > 1.0f ? batch_ / 2 : batch_;
+        a.cfg_scale = p.cfg_scale;
+        a.allowed = p.d_allowed;
+        a.n_allowed = p.d_allowed ? p.n_allowed : 0;
+        a.stop_id = p.stop_id < 0 ? -1 : p.stop_id;
+        a.pre_temperature = p.pre_temperature;
+        a.repetition_penalty = p.repetition_penalty;
+        a.seen = d_seen;
+        a.ld_seen = vocab;
+        a.top_k = p.top_k;
+        a.top_p = p.top_p;
+        a.temperature = p.temperature;
+        sel_work_.ensure(lm_select_work_floats(a.S, lm_select_candidates(vocab, p.n_allowed, p.d_allowed != nullptr)) * 4);
+        a.work = sel_work_.as<float>();
+        return a;
+    }
+
+    void select(const ace_mi_lm_sample_params& p, const float* d_logits, const float* d_uniform, uint8_t* d_seen,
+                int n_emitted, bool force_stop, int32_t* d_tokens, hipStream_t s) {
+        LmSelectArgs a = select_args(p, d_logits, d_seen);
+        a.block_stop = a.stop_id >= 0 && n_emitted < p.min_tokens;
+        a.force_stop = force_stop;
+        a.n_emitted = n_emitted;
+        a.uniform = d_uniform;
+        a.tokens = d_tokens;
+        launch_lm_select(a, s);
+    }
+
+    // the caller has checked the arguments and the capacity; returns *n_out
+    int generate(const ace_mi_lm_sample_params& p, float* d_logits, int n_max, const float* d_uniform, uint8_t* d_seen,
+                 int32_t* d_tokens, hipStream_t s) {
+        LmSelectArgs a = select_args(p, d_logits, d_seen);
+        sel_next_.ensure((size_t)LM_MAX_BATCH * 4);
+        sel_done_.ensure((size_t)(1 + LM_MAX_BATCH) * 4);
+        if (!d_uniform && p.temperature > 0.0f) {
+            std::vector<float> u((size_t)n_max * a.S);
+            std::mt19937_64 gen(p.seed);
+            for (float& v : u) v = (float)(gen() >> 40) * (1.0f / 16777216.0f);
+            sel_uni_.ensure(u.size() * 4);
+            ACEMI_HIP(hipDeviceSynchronize());  // an earlier loop, on any stream, may still read the buffer
+            ACEMI_HIP(hipMemcpy(sel_uni_.p, u.data(), u.size() * 4, hipMemcpyHostToDevice));
+            d_uniform = sel_uni_.as<float>();
+        }
+        const bool stops = a.stop_id >= 0;
+        const bool poll = stops && p.min_tokens < n_max;
+        static const int32_t zeros[1 + LM_MAX_BATCH] = {};
+        if (stops) ACEMI_HIP(hipMemcpyAsync(sel_done_.p, zeros, sizeof(zeros), hipMemcpyHostToDevice, s));
+        a.next_ids = sel_next_.as<int32_t>();
+        a.done = stops ? sel_done_.as<int32_t>() : nullptr;
+        a.token_stride = n_max;
+        int first_stop = 0;
+        const int len0 = len_;
+        try {
+            first_stop = run_loop(a, p, d_logits, n_max, d_uniform, d_tokens, stops, poll, s);
+        } catch (...) {
+            len_ = len0;  // the entry reports ACE_GGML_ERR with the cache length it found; the slots past it are scratch
+            throw;
+        }
+        return first_stop > 0 ? first_stop : n_max;
+    }
+
    private:
+    int run_loop(LmSelectArgs& a, const ace_mi_lm_sample_params& p, float* d_logits, int n_max, const float* d_uniform,
+                 int32_t* d_tokens, bool stops, bool poll, hipStream_t s) {
+        int first_stop = 0;
+        for (int t = 0; t < n_max; ++t) {
+            a.block_stop = stops && t < p.min_tokens;
+            a.n_emitted = t;
+            a.uniform = d_uniform ? d_uniform + (size_t)t * a.S : nullptr;
+            a.tokens = d_tokens + t;
+            launch_lm_select(a, s);
+            if (poll && (t + 1) % LM_STOP_POLL == 0 && t + 1 < n_max && (first_stop = read_done(s)) != 0) break;
+            if (t + 1 < n_max) {
+                step(a.next_ids, nullptr, d_logits, s);
+                ++len_;
+            }
+        }
+        if (poll && first_stop == 0) first_stop = read_done(s);
+        return first_stop;
+    }
+
+    // the `done` word of the loop through a pinned host word: async copy, event, wait
+    int read_done(hipStream_t s) {
+        if (!pinned_) alloc_pinned();
+        if (!done_ev_) ACEMI_HIP(hipEventCreateWithFlags(&done_ev_, hipEventDisableTiming));
+        ACEMI_HIP(hipMemcpyAsync(pinned_, sel_done_.p, 4, hipMemcpyDeviceToHost, s));
+        ACEMI_HIP(hipEventRecord(done_ev_, s));
+        ACEMI_HIP(hipEventSynchronize(done_ev_));
+        return *pinned_;
+    }
+#ifdef __HIP__
+    void alloc_pinned() { ACEMI_HIP(hipHostMalloc(reinterpret_cast<void**>(&pinned_), 16, hipHostMallocDefault)); }
+    void free_pinned() {
+        if (pinned_) (void)hipHostFree(pinned_);
+        pinned_ = nullptr;
+    }
+#else  // the host build has no pinned memory to ask for
+    void alloc_pinned() { pinned_ = static_cast<int32_t*>(std::calloc(4, 4)); }
+    void free_pinned() {
+        std::free(pinned_);
+        pinned_ = nullptr;
+    }
+#endif
+
     LmQkvPostArgs post_args(int li, const float* qkv, int ld) {
         const TextConfig& c = model_.cfg;
         const DevLayer& ly = model_.layers[li];
@@ -247,6 +379,9 @@ class LmEngine {
     TextModel model_;
     BlockRunner blocks_;
     DevBuf kc_, vc_, kmask_, cos_, sin_, x_, act_, act2_, qkv_, q_, attn_, part_, xn_, xh_;
+    DevBuf sel_work_, sel_next_, sel_done_, sel_uni_;  // selection scratch, the next step's ids, the stop words, uniforms
+    int32_t* pinned_ = nullptr;
+    hipEvent_t done_ev_ = nullptr;
     int batch_ = 0, capacity_ = 0, len_ = 0, rope_n_ = 0;
 };
 
@@ -341,6 +476,71 @@ ace_ggml_status ace_mi_lm_forward(ace_ggml_context* ctx, const int32_t* d_ids, c
         e->forward(d_ids, d_mask, n, d_logits, s);
     } catch (const std::exception& ex) {
         return set_error(ctx, ACE_GGML_ERR, std::string("lm forward failed: ") + ex.what());
+    }
+    return ACE_GGML_OK;
+}
+
+namespace {
+// the argument checks of ace_mi_lm_select / ace_mi_lm_generate; OK, or the status with the message set
+ace_ggml_status lm_check_sample(ace_ggml_context* ctx, acemi::LmEngine* e, const ace_mi_lm_sample_params* p, int n_emitted,
+                                bool force_stop, const char* where) {
+    int first = -1;
+    if (p->d_allowed && p->n_allowed == 1 && p->stop_id >= 0) {
+        try {
+            bind_device(ctx);
+            ACEMI_HIP(hipMemcpy(&first, p->d_allowed, 4, hipMemcpyDeviceToHost));
+        } catch (const std::exception& ex) {
+            return set_error(ctx, ACE_GGML_ERR, std::string(where) + ": " + ex.what());
+        }
+    }
+    if (const char* why = e->check_sample(*p, n_emitted, force_stop, first))
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, std::string(where) + ": " + why);
+    return ACE_GGML_OK;
+}
+}  // namespace
+
+ace_ggml_status ace_mi_lm_select(ace_ggml_context* ctx, const ace_mi_lm_sample_params* params, const float* d_logits,
+                                 const float* d_uniform, uint8_t* d_seen, int32_t n_emitted, int32_t force_stop,
+                                 int32_t* d_tokens, void* stream) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->lm) return set_error(ctx, ACE_GGML_ERR, "lm not loaded");
+    if (!params || !d_logits || !d_tokens || n_emitted < 0 || (params->temperature > 0.0f && !d_uniform))
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm select: null pointer or n_emitted < 0");
+    acemi::LmEngine* e = lm_of(ctx);
+    if (e->batch() <= 0) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm select: ace_mi_lm_begin was not called");
+    const ace_ggml_status st = lm_check_sample(ctx, e, params, n_emitted, force_stop != 0, "lm select");
+    if (st != ACE_GGML_OK) return st;
+    try {
+        bind_device(ctx);
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+        e->select(*params, d_logits, d_uniform, d_seen, n_emitted, force_stop != 0, d_tokens, s);
+    } catch (const std::exception& ex) {
+        return set_error(ctx, ACE_GGML_ERR, std::string("lm select failed: ") + ex.what());
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_lm_generate(ace_ggml_context* ctx, const ace_mi_lm_sample_params* params, float* d_logits,
+                                   int32_t n_max, const float* d_uniform, uint8_t* d_seen, int32_t* d_tokens,
+                                   int32_t* n_out, void* stream) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->lm) return set_error(ctx, ACE_GGML_ERR, "lm not loaded");
+    if (!params || !d_logits || !d_tokens || !n_out)
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm generate: null pointer");
+    acemi::LmEngine* e = lm_of(ctx);
+    if (e->batch() <= 0) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm generate: ace_mi_lm_begin was not called");
+    if (n_max < 1) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm generate: n_max < 1");
+    if ((int64_t)e->len() + n_max - 1 > e->capacity())
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm generate: exceeds the cache capacity");
+    const ace_ggml_status st = lm_check_sample(ctx, e, params, 0, false, "lm generate");
+    if (st != ACE_GGML_OK) return st;
+    try {
+        bind_device(ctx);
+        acemi::gemm_splitk_check();
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+        *n_out = e->generate(*params, d_logits, n_max, d_uniform, d_seen, d_tokens, s);
+    } catch (const std::exception& ex) {
+        return set_error(ctx, ACE_GGML_ERR, std::string("lm generate failed: ") + ex.what());
     }
     return ACE_GGML_OK;
 }

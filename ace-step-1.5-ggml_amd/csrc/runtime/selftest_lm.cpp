@@ -248,6 +248,68 @@ ace_ggml_status ace_mi_kernel_lm_prefill_kv(int32_t B, int32_t hq, int32_t hkv, 
     return ACE_GGML_OK;
 }
 
+ace_ggml_status ace_mi_kernel_lm_select(const ace_mi_kernel_lm_select_args* g) {
+    using namespace acemi;
+    if (!g || g->B < 1 || g->B > LM_MAX_BATCH || g->vocab < 1 || g->ld_logits < g->vocab || !g->logits || !g->tokens ||
+        g->token_stride < 1)
+        return ACE_GGML_ERR_INVALID_ARG;
+    const bool mix = g->cfg_scale > 1.0f;
+    if (mix && g->B % 2 != 0) return ACE_GGML_ERR_INVALID_ARG;
+    const int S = mix ? g->B / 2 : g->B;
+    if ((g->allowed && g->n_allowed < 1) || g->stop_id >= g->vocab || (g->force_stop && g->stop_id < 0) ||
+        (g->temperature > 0.0f && !g->uniform) || (g->seen && g->ld_seen < g->vocab) ||
+        (g->processed && g->ld_processed < g->vocab))
+        return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const int n_cand = lm_select_candidates(g->vocab, g->n_allowed, g->allowed != nullptr);
+        const size_t n_seen = (size_t)S * g->ld_seen, n_tok = (size_t)S * g->token_stride * 4;
+        const size_t n_proc = (size_t)S * g->ld_processed * 4;
+        DevMem dl(g->logits, (size_t)g->B * g->ld_logits * 4), da(g->allowed, (size_t)g->n_allowed * 4);
+        DevMem du(g->uniform, (size_t)S * 4), ds(g->seen, n_seen), dt(g->tokens, n_tok);
+        DevMem dn(g->next_ids, (size_t)g->B * 4), dd(g->done, (size_t)(1 + S) * 4), dp(g->processed, n_proc);
+        DevMem dw(lm_select_work_floats(S, n_cand) * 4);
+        LmSelectArgs a;
+        a.logits = dl.as<float>();
+        a.ld_logits = g->ld_logits;
+        a.vocab = g->vocab;
+        a.S = S;
+        a.cfg_scale = g->cfg_scale;
+        a.allowed = g->allowed ? da.as<int32_t>() : nullptr;
+        a.n_allowed = g->allowed ? g->n_allowed : 0;
+        a.stop_id = g->stop_id < 0 ? -1 : g->stop_id;
+        a.block_stop = g->block_stop != 0;
+        a.force_stop = g->force_stop != 0;
+        a.n_emitted = g->n_emitted;
+        a.pre_temperature = g->pre_temperature;
+        a.repetition_penalty = g->repetition_penalty;
+        a.seen = g->seen ? ds.as<uint8_t>() : nullptr;
+        a.ld_seen = g->ld_seen;
+        a.top_k = g->top_k;
+        a.top_p = g->top_p;
+        a.temperature = g->temperature;
+        a.uniform = g->uniform ? du.as<float>() : nullptr;
+        a.work = dw.as<float>();
+        a.tokens = dt.as<int32_t>();
+        a.token_stride = g->token_stride;
+        a.next_ids = g->next_ids ? dn.as<int32_t>() : nullptr;
+        a.done = g->done ? dd.as<int32_t>() : nullptr;
+        a.processed = g->processed ? dp.as<float>() : nullptr;
+        a.ld_processed = g->ld_processed;
+        launch_lm_select(a, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dt.to_host(g->tokens, n_tok);
+        if (g->seen) ds.to_host(g->seen, n_seen);
+        if (g->next_ids) dn.to_host(g->next_ids, (size_t)g->B * 4);
+        if (g->done) dd.to_host(g->done, (size_t)(1 + S) * 4);
+        if (g->processed) dp.to_host(g->processed, n_proc);
+        if (g->chains) lm_select_chains(n_cand, g->chains);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_select: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
 ace_ggml_status ace_mi_kernel_lm_attention(int32_t out_type, int32_t B, int32_t hq, int32_t hkv, int32_t capacity,
                                            int32_t nk, float scale, const float* q, const uint16_t* k_cache,
                                            const uint16_t* v_cache, const int32_t* key_mask, uint16_t* out_u16) {

@@ -212,7 +212,8 @@ ACE_GGML_API ace_ggml_status ace_mi_build_condition(ace_ggml_context* ctx, const
 /* ---- the 5 Hz audio-code language model (acestep/llm_inference.py): a HF Qwen3ForCausalLM with a KV cache, driven
  * the way the reference's `pt` backend drives transformers: one prefill `model(input_ids, attention_mask,
  * use_cache=True)`, then single-token calls with `past_key_values` (llm_inference.py:345-367).  The engine supplies
- * the last position's logits; the constrained-decoding FSM, CFG mixing and sampling stay with the caller.
+ * the last position's logits; the constrained-decoding FSM stays with the caller, and so do CFG mixing and sampling
+ * unless the caller uses ace_mi_lm_select / ace_mi_lm_generate below.
  * d_* are device pointers and the forward is stream-ordered like ace_mi_dit_forward_batched. ---- */
 typedef struct ace_mi_lm_info {
     int32_t vocab_size;
@@ -251,6 +252,67 @@ ACE_GGML_API ace_ggml_status ace_mi_lm_forward(ace_ggml_context* ctx, const int3
                                                int32_t n, float* d_logits, void* stream);
 /* Cache length back to 0 (batch and capacity kept). */
 ACE_GGML_API ace_ggml_status ace_mi_lm_reset(ace_ggml_context* ctx);
+
+/* ---- token selection and the engine-side decode loop (kernels/lm_sample.hip): what the reference's loops do to the
+ * logits between two forwards in the audio-code phase, on the GPU.  `batch` rows of logits give S sampled sequences:
+ * cfg_scale > 1 mixes row s (conditional) with row s + S (unconditional), S = batch / 2; otherwise S = batch.
+ * Per sequence, in this order, every arithmetic step one separately rounded f32 operation:
+ *   1. z = u + cfg_scale * (c - u) (cfg_scale > 1), else z = logits
+ *   2. candidates: the ids of d_allowed (ascending int32, device; NULL = the whole vocabulary), everything else
+ *      -inf; stop_id >= 0 with n_emitted < min_tokens removes stop_id; force_stop leaves only stop_id; a NaN counts
+ *      as -inf
+ *   3. pre_temperature > 0: z = z / pre_temperature (the constrained processor's phase temperature)
+ *   4. repetition_penalty != 1 and d_seen given (bytes [S][vocab], non-zero = seen): z < 0 ? z * p : z / p
+ *   5. 0 < top_k < candidates: remove z < the k-th largest z (values equal to it stay)
+ *   6. 0 < top_p < 1: with q = softmax(z) over the survivors, keep a value v iff the mass of the survivors strictly
+ *      greater than v is <= top_p (equal values stay or go together; the maximum always stays)
+ *   7. temperature > 0: p = softmax(z / temperature) over the kept ids; the token is the smallest kept id whose
+ *      inclusive cumulative mass, ids ascending, exceeds u * sum(p) (the largest kept id if none does), u in [0, 1)
+ *      one f32 per sequence.  temperature <= 0: the argmax, lowest id among equal maxima.
+ *   8. the token goes to d_tokens; d_seen[s][token] = 1 where given.
+ * If every candidate is -inf the first candidate id is returned. ---- */
+typedef struct ace_mi_lm_sample_params {
+    float cfg_scale;
+    float pre_temperature;
+    float repetition_penalty;
+    int32_t top_k;
+    float top_p;
+    float temperature;
+    const int32_t* d_allowed;   /* device, ascending, or NULL */
+    int32_t n_allowed;
+    int32_t stop_id;            /* < 0: none */
+    int32_t min_tokens;
+    uint64_t seed;              /* ace_mi_lm_generate with d_uniform == NULL */
+} ace_mi_lm_sample_params;
+/* One selection on the logits [batch][vocab] of the last forward, for callers that keep their own loop: d_uniform [S]
+ * f32 (may be NULL when temperature <= 0), d_seen or NULL, n_emitted = tokens emitted so far (step 2), force_stop != 0
+ * leaves only stop_id, d_tokens [S] int32.  Stream-ordered like ace_mi_lm_forward.  ACE_GGML_ERR_INVALID_ARG: see
+ * ace_mi_lm_generate. */
+ACE_GGML_API ace_ggml_status ace_mi_lm_select(ace_ggml_context* ctx, const ace_mi_lm_sample_params* params,
+                                              const float* d_logits, const float* d_uniform, uint8_t* d_seen,
+                                              int32_t n_emitted, int32_t force_stop, int32_t* d_tokens, void* stream);
+/* The decode loop in the engine.  Precondition: the prompt is in the cache (ace_mi_lm_forward) and d_logits
+ * [batch][vocab] holds the logits that forward wrote; the buffer is then scratch for the loop's own steps.  Token t <
+ * n_max: select on d_logits with n_emitted = t, then (unless t is the last) one decode step that appends the token to
+ * both rows of a pair, NULL mask, and writes d_logits again; all on `stream`, no host synchronisation per token.
+ * d_tokens [S][n_max] int32.  d_uniform [n_max][S] f32 or NULL: the host then draws n_max * S values from
+ * std::mt19937_64(params->seed), in that order, value = (x >> 40) * 2^-24 for each 64-bit output x, into a device
+ * buffer before the loop.  A sequence that has emitted stop_id keeps emitting it.
+ * stop_id >= 0 and min_tokens < n_max: after every 16th token the host reads a device word (pinned buffer, async
+ * copy, event wait) and stops enqueuing once a sequence has emitted stop_id; *n_out = 1 + the index of the first token
+ * at which any sequence emitted it (else n_max), entries of d_tokens past *n_out are unspecified, and the cache then
+ * holds the prompt and the min(n_max, 16 * ceil(*n_out / 16)) - 1 tokens fed back.  Otherwise *n_out = n_max and the
+ * cache grows by n_max - 1 (min_tokens == n_max with a stop_id is the duration-constrained case: the stop token is
+ * never a candidate and nothing is polled; the caller appends EOS).  The call returns after a final read of that word.
+ * ACE_GGML_ERR_INVALID_ARG, cache and cache_len unchanged: cache_len + n_max - 1 > capacity, n_max < 1, cfg_scale > 1
+ * with an odd batch, n_allowed < 1 with a list, stop_id >= vocab, force_stop without a stop_id, or a candidate set
+ * that step 2 empties (a one-id list, or a one-id vocabulary, that is the blocked stop_id).  ACE_GGML_ERR "lm not
+ * loaded" before ace_mi_load_lm.  ACE_GGML_ERR from a failed launch or copy inside the loop: cache_len is back at its
+ * value on entry, d_logits and d_tokens are unspecified, and the caller starts over from ace_mi_lm_begin or
+ * ace_mi_lm_reset. */
+ACE_GGML_API ace_ggml_status ace_mi_lm_generate(ace_ggml_context* ctx, const ace_mi_lm_sample_params* params,
+                                                float* d_logits, int32_t n_max, const float* d_uniform,
+                                                uint8_t* d_seen, int32_t* d_tokens, int32_t* n_out, void* stream);
 
 /* The x_T stream of the reference generator (std::mt19937(seed) + std::normal_distribution<float>,
  * acestep_ggml.cpp:2043-2048) as the generate entries draw it: n values into out (host). */

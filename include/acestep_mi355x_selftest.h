@@ -149,6 +149,32 @@ ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_attention(int32_t out_type, int32_
                                                         int32_t capacity, int32_t nk, float scale, const float* q,
                                                         const uint16_t* k_cache, const uint16_t* v_cache,
                                                         const int32_t* key_mask, uint16_t* out_u16);
+/* Token selection (kernels/lm_sample.hip; semantics: ace_mi_lm_select in acestep_mi355x.h) on host arrays with padded
+ * leading dimensions: logits [B][ld_logits] (S = B, or B / 2 when cfg_scale > 1), allowed [n_allowed] or NULL, uniform
+ * [S] or NULL, seen [S][ld_seen] bytes or NULL (in-out), tokens [S * token_stride] (in-out: word s * token_stride is
+ * written), next_ids [B] or NULL (in-out), done [1 + S] or NULL (in-out: [0] = 1 + n_emitted at the first stop, [1 + s]
+ * = sequence s has stopped), processed [S][ld_processed] or NULL (in-out: the logits after the top-p cut, -inf where
+ * removed, columns < vocab only).  block_stop: the caller's n_emitted < min_tokens.  chains (int32 [3], may be NULL)
+ * receives the longest f32 addition chains behind a top-p mass [0], behind the draw's total [1] and behind a cumulative
+ * value of the draw [2]. */
+typedef struct ace_mi_kernel_lm_select_args {
+    int32_t B, vocab, ld_logits;
+    float cfg_scale, pre_temperature, repetition_penalty;
+    int32_t top_k;
+    float top_p, temperature;
+    int32_t n_allowed, stop_id, block_stop, force_stop, n_emitted;
+    int32_t ld_seen, token_stride, ld_processed;
+    const float* logits;
+    const int32_t* allowed;
+    const float* uniform;
+    uint8_t* seen;
+    int32_t* tokens;
+    int32_t* next_ids;
+    int32_t* done;
+    float* processed;
+    int32_t* chains;
+} ace_mi_kernel_lm_select_args;
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_select(const ace_mi_kernel_lm_select_args* args);
 /* Dequant-fused GEMM micro-benchmark: average ms per launch (HIP events). */
 ACE_GGML_API ace_ggml_status ace_mi_bench_gemm_q(int32_t qtype, int32_t epi, int32_t variant, int32_t M, int32_t N,
                                                  int32_t K, int32_t iters, float* avg_ms);

@@ -15,8 +15,18 @@ Each step is timed on its own with a pair of events after warm-up steps; the tab
 (every 2-D tensor in random valid blocks of the type, norms F32, tied head: the step then runs kernels/lm_decode_q.hip
 on the block planes, 1.125 / 0.75 / 1.25 bytes per weight); torch eager is measured for the dense checkpoint only.
 
+--generate measures the audio-code phase instead (B = 2 as one CFG pair, cache 1024, candidates = 64 000 contiguous ids
++ EOS, top-k off / 50 x top-p off / 0.9), ms per token of
+  (a) the engine step alone (ace_mi_lm_forward, n = 1);
+  (b) the path without the engine loop: the step plus the per-token torch work of the reference's loops restated here
+      (CFG mix, mask add, temperature, topk, the full sort / softmax / cumsum / scatter of top-p, softmax, multinomial,
+      .item(), the EOS test and the two torch.cat that grow the ids and the mask);
+  (c) ace_mi_lm_generate: --calls calls of --steps tokens each, the call's wall time / tokens (the prefill is outside);
+  and the selection kernel alone (ace_mi_lm_select).  (a), (b) and the kernel are timed per token with event pairs.
+
   python tools/lm_decode_time.py --models 0.6b,1.7b --steps 30 --warmup 5 [--gguf Q8_0,Q4_K,Q6_K] [--no-torch]
-                                 [--json out.json]"""
+                                 [--json out.json]
+  python tools/lm_decode_time.py --generate --models 0.6b,1.7b --steps 30 --warmup 5 [--calls 5] [--json out.json]"""
 import argparse
 import json
 import os
@@ -84,6 +94,79 @@ def engine_times(ckpt, cfg, Bs, lens, warm, steps):
     return out
 
 
+def generate_times(ckpt, cfg, warm, steps, calls, cache=1024, n_codes=64000):
+    """rows of the --generate table for one checkpoint"""
+    import time
+    import torch
+    from acestep_mi355x.capi import GGMLCAPIBridge
+    br = GGMLCAPIBridge()
+    br.load_lm(ckpt)
+    V, B, S, cfg_scale, temp = cfg["vocab_size"], 2, 1, 2.0, 0.85
+    eos = V - n_codes - 10
+    allowed = torch.cat([torch.tensor([eos]), torch.arange(V - n_codes, V)]).to(torch.int32).cuda()
+    mask = torch.full((1, V), float("-inf"), device="cuda")
+    mask[0, allowed.long()] = 0
+    g = torch.Generator().manual_seed(0)
+    prompt = torch.randint(0, V, (B, cache), generator=g, dtype=torch.int32).cuda()
+    rows = []
+
+    def fresh():
+        br.lm_begin(B, cache + (warm + steps) * (calls + 2))
+        return br.lm_forward(prompt)
+
+    for top_k in (0, 50):
+        for top_p in (1.0, 0.9):
+            kw = dict(allowed_ids=allowed, stop_id=eos, cfg_scale=cfg_scale, pre_temperature=temp, temperature=temp,
+                      top_k=top_k, top_p=top_p)
+            logits = fresh()
+            tok = prompt[:, :1].contiguous()
+            a_ms = time_steps(lambda: br.lm_forward(tok), warm, steps)
+            u = torch.full((S,), 0.5, device="cuda")
+            k_ms = time_steps(lambda: br.lm_select(logits, uniforms=u, min_tokens=10 ** 6, **kw), warm, steps)
+            state = dict(ids=prompt.long(), am=torch.ones((B, cache), dtype=torch.long, device="cuda"), logits=fresh())
+
+            def parent():
+                x = state["logits"]
+                z = x[S:].float() + cfg_scale * (x[:S].float() - x[S:].float())
+                z = z + mask
+                z[:, eos] = float("-inf")
+                z = z / temp
+                gone = torch.full_like(z, float("-inf"))
+                if top_k:       # one topk launch, then the mask
+                    floor = torch.topk(z, top_k, dim=-1).values.amin(dim=-1, keepdim=True)
+                    z = torch.where(z >= floor, z, gone)
+                if top_p < 1.0:  # the full descending sort, softmax and running sum, and the scatter back to id order
+                    order = torch.argsort(z, dim=-1, descending=True)
+                    mass = torch.cumsum(torch.softmax(torch.gather(z, 1, order).float(), dim=-1), dim=-1)
+                    before = torch.roll(mass, 1, dims=-1)       # mass strictly ahead of each rank
+                    before[:, 0] = 0.0
+                    drop = torch.zeros_like(z, dtype=torch.bool).scatter(1, order, before > top_p)
+                    z = torch.where(drop, gone, z)
+                nxt = torch.multinomial(torch.softmax(z.float() / temp, dim=-1), num_samples=1).squeeze(1)
+                for b in range(S):
+                    nxt[b].item()
+                bool(torch.any(nxt == eos))
+                col = nxt.unsqueeze(1).repeat(2, 1)
+                state["ids"] = torch.cat([state["ids"], col], dim=1)
+                state["am"] = torch.cat([state["am"], torch.ones((B, 1), device="cuda", dtype=torch.long)], dim=1)
+                state["logits"] = br.lm_forward(col)
+            b_ms = time_steps(parent, warm, steps)
+            logits = fresh()
+            br.lm_generate(logits, warm, seed=1, min_tokens=warm, **kw)
+            per = []
+            for i in range(calls):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                br.lm_generate(logits, steps, seed=2 + i, min_tokens=steps, **kw)
+                torch.cuda.synchronize()
+                per.append((time.perf_counter() - t0) * 1e3 / steps)
+                br.lm_forward(tok)      # the last token of a call is not fed back: the next call needs fresh logits
+            c_ms = dict(median=statistics.median(per), min=min(per), max=max(per))
+            rows.append(dict(top_k=top_k, top_p=top_p, step=a_ms, parent=b_ms, generate=c_ms, select=k_ms))
+    br.close()
+    return rows
+
+
 def torch_times(ckpt, cfg, Bs, lens, warm, steps):
     import torch
     from safetensors.torch import load_file
@@ -128,7 +211,11 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--gguf", default="", help="comma-separated block types (Q8_0, Q4_K, Q6_K) to time as GGUF files")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--generate", action="store_true", help="time the audio-code phase: step, per-token torch path, engine loop")
+    ap.add_argument("--calls", type=int, default=5)
     a = ap.parse_args()
+    if a.generate:
+        return main_generate(a)
     Bs, lens = [int(x) for x in a.batch.split(",")], [int(x) for x in a.cache.split(",")]
     rows = []
     print("| model | B | cache | engine ms/step median (min-max) | bytes/step MB (weights + cache) | bytes / 8.0 TB/s ms "
@@ -164,6 +251,28 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
         with open(a.json, "w") as f:
             json.dump(rows, f, indent=1)
+
+
+def main_generate(a):
+    fmt = lambda t: f"{t['median']:.3f} ({t['min']:.3f}-{t['max']:.3f})"
+    print("| model | top-k | top-p | (a) step ms | (b) step + torch per-token ms | (c) lm_generate ms/token | select alone ms "
+          "| (c) - (a) | (c) <= (b) |")
+    print("|---|---|---|---|---|---|---|---|---|")
+    out = []
+    for name in a.models.split(","):
+        cfg = dict(SHAPES[name], vocab_size=a.vocab)
+        with tempfile.TemporaryDirectory(prefix="acemi_lmtime_") as d:
+            _write(d, cfg)
+            for r in generate_times(d, cfg, a.warmup, a.steps, a.calls):
+                out.append(dict(r, model=name))
+                print(f"| {name} | {r['top_k'] or 'off'} | {r['top_p'] if r['top_p'] < 1 else 'off'} | {fmt(r['step'])} | "
+                      f"{fmt(r['parent'])} | {fmt(r['generate'])} | {fmt(r['select'])} | "
+                      f"{r['generate']['median'] - r['step']['median']:.3f} | "
+                      f"{'yes' if r['generate']['median'] <= r['parent']['median'] else 'NO'} |", flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
 
 
 def _write(d, cfg):
