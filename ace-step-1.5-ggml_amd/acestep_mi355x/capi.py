@@ -55,7 +55,8 @@ SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_ben
                     "ace_mi_gemm_resolve", "ace_mi_gemm_variant_row", "ace_mi_gemm_variant_arg_ok",
                     "ace_mi_kernel_lm_skinny", "ace_mi_kernel_lm_embed", "ace_mi_kernel_lm_qkv_post",
                     "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention", "ace_mi_kernel_lm_skinny_q",
-                    "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_select")
+                    "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_select",
+                    "ace_mi_kernel_conv_gemm", "ace_mi_kernel_conv_out", "ace_mi_kernel_pack_f16")
 
 # qtype codes of ace_mi_quantize & co. (names as parse_quant_type, acestep_dit_model.cpp:27-37)
 QTYPES = {"q8_0": 1, "q4_k": 2, "q6_k": 3,
@@ -119,6 +120,14 @@ class AceMiKernelLmSelectArgs(ctypes.Structure):
                 ("logits", ctypes.c_void_p), ("allowed", ctypes.c_void_p), ("uniform", ctypes.c_void_p),
                 ("seen", ctypes.c_void_p), ("tokens", ctypes.c_void_p), ("next_ids", ctypes.c_void_p),
                 ("done", ctypes.c_void_p), ("processed", ctypes.c_void_p), ("chains", ctypes.c_void_p)]
+
+
+class AceMiConvGemmArgs(ctypes.Structure):
+    """ace_mi_conv_gemm_args (include/acestep_mi355x_selftest.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "T_in", "Cin", "taps", "dil", "pad", "in_stride", "M", "N", "Cout", "up", "crop", "T_out", "resid", "store_x",
+        "items", "guard")] + [(n, ctypes.c_void_p) for n in (
+            "S", "W", "bias", "snake_ea", "snake_eb", "W2", "bias2", "snake2_ea", "snake2_eb", "X", "S_out")]
 
 
 class AceMiBlockSeg(ctypes.Structure):
@@ -338,6 +347,7 @@ def load_selftest_library() -> ctypes.CDLL:
     lib.ace_mi_bench_dequant_blocks.restype = ctypes.c_int
     _bind_gemm_variants(lib)
     _bind_lm_kernels(lib)
+    _bind_vae_kernels(lib)
     _SELFTEST = lib
     return lib
 
@@ -1221,6 +1231,102 @@ def kernel_lm_select(logits: np.ndarray, cfg_scale=1.0, pre_temperature=0.0, rep
         chains=ptr(chains))
     _lm_status("select", lib.ace_mi_kernel_lm_select(ctypes.byref(g)))
     return {"tokens": tok, "seen": sn, "next_ids": nx, "done": dn, "processed": pr, "chains": chains}
+
+
+def _bind_vae_kernels(lib):
+    i32, fp, u16p = ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_uint16)
+    lib.ace_mi_kernel_conv_gemm.argtypes = [ctypes.POINTER(AceMiConvGemmArgs)]
+    lib.ace_mi_kernel_conv_out.argtypes = [u16p, i32, i32, u16p, i32, fp, i32]
+    lib.ace_mi_kernel_pack_f16.argtypes = [fp, ctypes.c_int64, i32, i32, u16p]
+    for name in ("conv_gemm", "conv_out", "pack_f16"):
+        getattr(lib, "ace_mi_kernel_" + name).restype = ctypes.c_int
+    return lib
+
+
+def _vae_lib(lib):
+    """`lib`: a loaded library that exports the VAE kernel entries (default: the GPU self-test library)."""
+    return _bind_vae_kernels(lib) if lib is not None else load_selftest_library()
+
+
+def kernel_conv_gemm(S_bits: np.ndarray, W_bits: np.ndarray, *, M: int, Cout: int, T_out: int, taps: int = 1, dil: int = 1,
+                     pad: int = 0, in_stride: int = 1, up: int = 1, crop: int = 0, bias=None, snake=None, W2_bits=None,
+                     bias2=None, snake2=None, X0=None, S_out0=None, resid: bool = False, store_x: bool = False,
+                     guard: int = 0, halo: bool = True, lib=None):
+    """One launch_conv_gemm (ConvGemmArgs of csrc/kernels.h) on host arrays: S_bits [items][T_in][Cin] and W_bits
+    [N][taps * Cin] fp16 words; bias [N] ([Cout] for up > 1), snake / snake2 = (ea, eb) f32 pairs, W2_bits [Cout][Cout],
+    bias2 [Cout]; X0 (float32) and S_out0 (uint16), either may be None, are flat arrays of guard + items * T_out * Cout +
+    guard elements holding the initial content.  halo=False runs with ACE_MI_VAE_HALO=0 (the generic staging for the
+    residual units' k7 convs); the variable is restored afterwards.  Returns (X, S_out) after the launch, guards
+    included (None where none was given).  Raises RuntimeError with the status on a refused call; the exception carries
+    the two arrays as the entry left them (.X, .S_out)."""
+    lib = _vae_lib(lib)
+    S = np.ascontiguousarray(S_bits, dtype=np.uint16)
+    W = np.ascontiguousarray(W_bits, dtype=np.uint16)
+    if S.ndim != 3 or W.ndim != 2:
+        raise ValueError("S_bits must be [items][T_in][Cin], W_bits [N][taps * Cin]")
+    items, T_in, Cin = S.shape
+    f32 = lambda a: None if a is None else np.ascontiguousarray(a, dtype=np.float32)
+    b, b2 = f32(bias), f32(bias2)
+    ea, eb = (None, None) if snake is None else (f32(snake[0]), f32(snake[1]))
+    ea2, eb2 = (None, None) if snake2 is None else (f32(snake2[0]), f32(snake2[1]))
+    W2 = None if W2_bits is None else np.ascontiguousarray(W2_bits, dtype=np.uint16)
+    X = None if X0 is None else np.array(X0, dtype=np.float32, order="C", copy=True)
+    So = None if S_out0 is None else np.array(S_out0, dtype=np.uint16, order="C", copy=True)
+    n = 2 * guard + items * T_out * Cout
+    for a in (X, So):
+        if a is not None and a.size != n:
+            raise ValueError(f"X0 / S_out0 must hold guard + items * T_out * Cout + guard = {n} elements")
+    ptr = lambda a: None if a is None else a.ctypes.data
+    g = AceMiConvGemmArgs(T_in=T_in, Cin=Cin, taps=taps, dil=dil, pad=pad, in_stride=in_stride, M=M, N=W.shape[0],
+                          Cout=Cout, up=up, crop=crop, T_out=T_out, resid=int(bool(resid)), store_x=int(bool(store_x)),
+                          items=items, guard=guard, S=ptr(S), W=ptr(W), bias=ptr(b), snake_ea=ptr(ea), snake_eb=ptr(eb),
+                          W2=ptr(W2), bias2=ptr(b2), snake2_ea=ptr(ea2), snake2_eb=ptr(eb2), X=ptr(X), S_out=ptr(So))
+    old = os.environ.get("ACE_MI_VAE_HALO")
+    if halo:
+        os.environ.pop("ACE_MI_VAE_HALO", None)
+    else:
+        os.environ["ACE_MI_VAE_HALO"] = "0"
+    try:
+        st = lib.ace_mi_kernel_conv_gemm(ctypes.byref(g))
+    finally:
+        if old is None:
+            os.environ.pop("ACE_MI_VAE_HALO", None)
+        else:
+            os.environ["ACE_MI_VAE_HALO"] = old
+    if st != ACE_GGML_OK:
+        err = RuntimeError(f"ace_mi_kernel_conv_gemm failed (status={st})")
+        err.X, err.S_out = X, So          # the arrays the entry was given, for a caller that checks they are untouched
+        raise err
+    return X, So
+
+
+def kernel_conv_out(S_bits: np.ndarray, W_bits: np.ndarray, out0: np.ndarray, guard: int = 0, lib=None) -> np.ndarray:
+    """launch_conv_out (decoder.conv2) on host arrays: S_bits [items][T][128] and W_bits [out_ch][7][128] fp16 words, out0
+    a flat float32 array of guard + items * T * out_ch + guard elements (the initial content).  Returns it after the launch."""
+    lib = _vae_lib(lib)
+    S = np.ascontiguousarray(S_bits, dtype=np.uint16)
+    W = np.ascontiguousarray(W_bits, dtype=np.uint16)
+    if S.ndim != 3 or S.shape[2] != 128 or W.ndim != 3 or W.shape[1:] != (7, 128):
+        raise ValueError("S_bits must be [items][T][128], W_bits [out_ch][7][128]")
+    out = np.array(out0, dtype=np.float32, order="C", copy=True)
+    if out.size != 2 * guard + S.shape[0] * S.shape[1] * W.shape[0]:
+        raise ValueError("out0 must hold guard + items * T * out_ch + guard elements")
+    st = lib.ace_mi_kernel_conv_out(_u16ptr(S), S.shape[1], S.shape[0], _u16ptr(W), W.shape[0], _fptr(out), guard)
+    if st != ACE_GGML_OK:
+        raise RuntimeError(f"ace_mi_kernel_conv_out failed (status={st})")
+    return out
+
+
+def kernel_pack_f16(x: np.ndarray, Cpad: int, lib=None) -> np.ndarray:
+    """x [rows][C] f32 -> fp16 words [rows][Cpad], columns >= C zero: pack_f16_kernel, or to_f16_kernel when Cpad == C.
+    The destination starts as 0x7FFF words."""
+    lib = _vae_lib(lib)
+    xx = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.full((xx.shape[0], Cpad), 0x7FFF, np.uint16)
+    st = lib.ace_mi_kernel_pack_f16(_fptr(xx), xx.shape[0], xx.shape[1], Cpad, _u16ptr(y))
+    if st != ACE_GGML_OK:
+        raise RuntimeError(f"ace_mi_kernel_pack_f16 failed (status={st})")
+    return y
 
 
 def kernel_gemm_q(a_bits: np.ndarray, w_blocks: np.ndarray, qtype: str, epi: int = 0, variant: int = -1,

@@ -786,3 +786,139 @@ ace_ggml_status ace_mi_gemm_variant_arg_ok(int32_t variant, int32_t allow_unchec
 }
 
 }  // extern "C"
+
+// ---- VAE conv kernels (kernels/vae.hip): one launch on host buffers, on a stream
+namespace {
+
+// a device copy of `n` elements of a host array (null host: null device pointer, nothing allocated)
+template <typename T>
+struct DevCopy {
+    std::unique_ptr<DevMem> m;
+    DevCopy(const T* host, size_t n) {
+        if (!host) return;
+        m = std::make_unique<DevMem>(n * sizeof(T));
+        ACEMI_HIP(hipMemcpy(m->p, host, n * sizeof(T), hipMemcpyHostToDevice));
+    }
+    T* get() const { return m ? static_cast<T*>(m->p) : nullptr; }
+};
+
+struct Stream {
+    hipStream_t s = nullptr;
+    Stream() { ACEMI_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+    ~Stream() {
+        if (s) (void)hipStreamDestroy(s);
+    }
+};
+
+}  // namespace
+
+extern "C" {
+
+ace_ggml_status ace_mi_kernel_conv_gemm(const ace_mi_conv_gemm_args* g) {
+    using namespace acemi;
+    if (!g) return ACE_GGML_ERR_INVALID_ARG;
+    // what the buffers are sized from; everything else is launch_conv_gemm's to refuse
+    const int dims[] = {g->T_in, g->Cin, g->taps, g->M, g->N, g->Cout, g->T_out, g->items, g->up, g->in_stride};
+    for (int d : dims)
+        if (d < 1 || d > (1 << 24)) return ACE_GGML_ERR_INVALID_ARG;
+    if (g->taps > 64 || g->guard < 0 || g->guard % 4 != 0 || g->guard > (1 << 24) || g->pad < 0 || g->crop < 0)
+        return ACE_GGML_ERR_INVALID_ARG;
+    if (!g->snake_ea != !g->snake_eb || !g->snake2_ea != !g->snake2_eb) return ACE_GGML_ERR_INVALID_ARG;
+    const int64_t nS =(int64_t)g->items * g->T_in * g->Cin, nW = (int64_t)g->N * g->taps * g->Cin;
+    const int64_t nP = (int64_t)g->items * g->T_out * g->Cout, nW2 = (int64_t)g->Cout * g->Cout;
+    if (nS >= (1LL << 31) || nW >= (1LL << 31) || nP >= (1LL << 31) || nW2 >= (1LL << 31)) return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const size_t nO = (size_t)nP + 2 * (size_t)g->guard;
+        DevCopy<uint16_t> dS(g->S, (size_t)nS), dW(g->W, (size_t)nW), dW2(g->W2, (size_t)nW2);
+        DevCopy<float> dB(g->bias, (size_t)(g->up > 1 ? g->Cout : g->N)), dEa(g->snake_ea, (size_t)g->Cout),
+            dEb(g->snake_eb, (size_t)g->Cout), dB2(g->bias2, (size_t)g->Cout), dEa2(g->snake2_ea, (size_t)g->N),
+            dEb2(g->snake2_eb, (size_t)g->N);
+        DevCopy<float> dX(g->X, nO);
+        DevCopy<uint16_t> dSo(g->S_out, nO);
+        DevMem zero(4096);  // VaeEngine::ensure(zero_, 4096)
+        ACEMI_HIP(hipMemset(zero.p, 0, 4096));
+        ACEMI_HIP(hipDeviceSynchronize());  // the uploads and the memset do not order against a non-blocking stream
+        ConvGemmArgs a;
+        a.S = dS.get();
+        a.zero = zero.as<uint16_t>();
+        a.W = dW.get();
+        a.T_in = g->T_in;
+        a.Cin = g->Cin;
+        a.taps = g->taps;
+        a.dil = g->dil;
+        a.pad = g->pad;
+        a.in_stride = g->in_stride;
+        a.M = g->M;
+        a.N = g->N;
+        a.bias = dB.get();
+        a.Cout = g->Cout;
+        a.up = g->up;
+        a.crop = g->crop;
+        a.T_out = g->T_out;
+        a.X = dX.get() ? dX.get() + g->guard : nullptr;
+        a.resid = g->resid;
+        a.store_x = g->store_x;
+        a.S_out = dSo.get() ? dSo.get() + g->guard : nullptr;
+        a.snake_ea = dEa.get();
+        a.snake_eb = dEb.get();
+        a.items = g->items;
+        a.W2 = dW2.get();
+        a.bias2 = dB2.get();
+        a.snake2_ea = dEa2.get();
+        a.snake2_eb = dEb2.get();
+        Stream st;
+        launch_conv_gemm(a, st.s);
+        ACEMI_HIP(hipStreamSynchronize(st.s));
+        if (g->X) ACEMI_HIP(hipMemcpy(g->X, dX.get(), nO * 4, hipMemcpyDeviceToHost));
+        if (g->S_out) ACEMI_HIP(hipMemcpy(g->S_out, dSo.get(), nO * 2, hipMemcpyDeviceToHost));
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_conv_gemm: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_kernel_conv_out(const uint16_t* S, int32_t T, int32_t items, const uint16_t* W, int32_t out_ch,
+                                       float* out, int32_t guard) {
+    using namespace acemi;
+    if (!S || !W || !out || T < 1 || items < 1 || (out_ch != 1 && out_ch != 2) || guard < 0 || guard > (1 << 24) ||
+        (int64_t)T * items >= (1LL << 24))
+        return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const size_t nO = (size_t)T * items * out_ch + 2 * (size_t)guard;
+        DevCopy<uint16_t> dS(S, (size_t)T * items * 128), dW(W, (size_t)out_ch * 7 * 128);
+        DevCopy<float> dO(out, nO);
+        ACEMI_HIP(hipDeviceSynchronize());
+        Stream st;
+        launch_conv_out(dS.get(), T, 128, dW.get(), out_ch, dO.get() + guard, st.s, items);
+        ACEMI_HIP(hipStreamSynchronize(st.s));
+        ACEMI_HIP(hipMemcpy(out, dO.get(), nO * 4, hipMemcpyDeviceToHost));
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_conv_out: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_kernel_pack_f16(const float* x, int64_t rows, int32_t C, int32_t Cpad, uint16_t* y) {
+    using namespace acemi;
+    if (!x || !y || rows < 1 || C < 1 || Cpad < C || rows * Cpad >= (1LL << 31)) return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        DevCopy<float> dx(x, (size_t)rows * C);
+        DevCopy<uint16_t> dy(y, (size_t)rows * Cpad);
+        ACEMI_HIP(hipDeviceSynchronize());
+        Stream st;
+        if (C == Cpad)
+            launch_to_f16(dx.get(), rows * C, dy.get(), st.s);
+        else
+            launch_pack_f16(dx.get(), rows, C, Cpad, dy.get(), st.s);
+        ACEMI_HIP(hipStreamSynchronize(st.s));
+        ACEMI_HIP(hipMemcpy(y, dy.get(), (size_t)rows * Cpad * 2, hipMemcpyDeviceToHost));
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_pack_f16: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+}  // extern "C"

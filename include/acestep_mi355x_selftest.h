@@ -175,6 +175,40 @@ typedef struct ace_mi_kernel_lm_select_args {
     int32_t* chains;
 } ace_mi_kernel_lm_select_args;
 ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_select(const ace_mi_kernel_lm_select_args* args);
+/* ---- VAE conv kernels (csrc/kernels/vae.hip through launch_conv_gemm / launch_conv_out / launch_pack_f16 /
+ * launch_to_f16 of csrc/kernels.h).  One launch each on host buffers, on a stream, blocking.
+ * conv_gemm: the integer fields are those of ConvGemmArgs.  S [items][T_in][Cin] and W [N][taps * Cin] fp16 words;
+ * bias [N] (transposed conv, up > 1: [Cout]), snake_ea / snake_eb [Cout], W2 [Cout][Cout] fp16, bias2 [Cout], snake2_ea /
+ * snake2_eb [N]: f32, any of them may be NULL.  X (f32) and S_out (fp16 words), either may be NULL, are host arrays of
+ * guard + items * T_out * Cout + guard elements: the kernel gets the pointer to the payload behind the first guard, the
+ * whole array is uploaded before and copied back after the launch, so a caller sees every word that was written.  guard
+ * must be a multiple of 4 (the kernel's 16-byte accesses).  The zero row the kernel stages for rows outside [0, T_in) is
+ * the 4096-byte zero buffer of VaeEngine.  ACE_MI_VAE_HALO is read by the launch.  INVALID_ARG: a dimension that no
+ * buffer can be sized from; ERR: what launch_conv_gemm refuses (message on stderr); X and S_out are untouched in both
+ * cases. */
+typedef struct ace_mi_conv_gemm_args {
+    int32_t T_in, Cin, taps, dil, pad, in_stride, M, N, Cout, up, crop, T_out, resid, store_x, items;
+    int32_t guard;
+    const uint16_t* S;
+    const uint16_t* W;
+    const float* bias;
+    const float* snake_ea;
+    const float* snake_eb;
+    const uint16_t* W2;
+    const float* bias2;
+    const float* snake2_ea;
+    const float* snake2_eb;
+    float* X;
+    uint16_t* S_out;
+} ace_mi_conv_gemm_args;
+ACE_GGML_API ace_ggml_status ace_mi_kernel_conv_gemm(const ace_mi_conv_gemm_args* args);
+/* decoder.conv2: S [items][T][128] fp16 words, W [out_ch][7][128] fp16 words, out = guard + items * T * out_ch + guard
+ * f32 (in-out, copied back whole). */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_conv_out(const uint16_t* S, int32_t T, int32_t items, const uint16_t* W,
+                                                    int32_t out_ch, float* out, int32_t guard);
+/* x [rows][C] f32 -> y [rows][Cpad] fp16 words (in-out), columns >= C zero: launch_pack_f16, or launch_to_f16 on the
+ * rows * C values when C == Cpad. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_pack_f16(const float* x, int64_t rows, int32_t C, int32_t Cpad, uint16_t* y);
 /* Dequant-fused GEMM micro-benchmark: average ms per launch (HIP events). */
 ACE_GGML_API ace_ggml_status ace_mi_bench_gemm_q(int32_t qtype, int32_t epi, int32_t variant, int32_t M, int32_t N,
                                                  int32_t K, int32_t iters, float* avg_ms);

@@ -699,8 +699,19 @@ void launch_sde(float* xt, const float* v, const float* noise, int64_t n, float 
 // ---------------------------------------------------------------- VAE
 void launch_conv_gemm(const ConvGemmArgs& a, hipStream_t) {
     ACEMI_CHECK(a.Cin % 64 == 0 && a.N % 128 == 0 && a.M >= 1 && a.taps >= 1, "conv_gemm: unsupported shape");
-    touch(a.zero, 64);  // the kernel stages out-of-range rows from 64 zero halves
+    // the rest of what the kernel's launch refuses
+    ACEMI_CHECK(a.S && a.W && a.zero, "conv_gemm: null operand");
+    ACEMI_CHECK(a.up <= 1 || a.N == a.up * a.Cout, "conv_gemm: transposed conv needs N = stride * Cout");
+    ACEMI_CHECK(a.up > 1 || a.N == a.Cout, "conv_gemm: N must equal Cout");
+    ACEMI_CHECK(!(a.resid || a.store_x) || a.X, "conv_gemm: null X");
     ACEMI_CHECK(a.items >= 1 && a.M % a.items == 0, "conv_gemm: rows must split evenly into the sequences");
+    ACEMI_CHECK(a.Cout % 4 == 0, "conv_gemm: output channels must be a multiple of 4");
+    if (a.W2)
+        ACEMI_CHECK(a.N == 128 && a.Cout == 128 && a.up <= 1 && a.snake2_ea && a.snake2_eb,
+                    "conv_gemm: the fused k1 conv needs Cout = N = 128 and a Snake between the convs");
+    // out-of-range rows are staged from the zero buffer: 64 halves (chunk * 8, chunk < 8) by the generic staging,
+    // 128 halves (hc * 8, hc < 16) by the halo staging; an epilogue without a residual reads 4 floats of it
+    touch(a.zero, 128);
     const int K = a.taps * a.Cin;
     const int Mi = a.M / a.items;
     std::vector<float> row((size_t)K);
