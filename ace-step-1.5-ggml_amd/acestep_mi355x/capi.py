@@ -30,7 +30,7 @@ ACE_GGML_ERR_UNSUPPORTED = 4
 EXPORTED_SYMBOLS = (
     "ace_ggml_create", "ace_ggml_destroy", "ace_ggml_last_error", "ace_ggml_load_dit", "ace_ggml_dit_forward",
     "ace_mi_create_on_device", "ace_mi_dit_get_info", "ace_mi_dit_weight_desc", "ace_mi_dit_forward_batched", "ace_mi_dit_sample",
-    "ace_mi_dit_sample_ex",
+    "ace_mi_dit_sample_ex", "ace_mi_dit_forward_capture",
     "ace_mi_profile_enable", "ace_mi_dit_set_attn_precision", "ace_mi_profile_reset", "ace_mi_profile_get", "ace_mi_probe_gemm",
     "ace_mi_synchronize", "ace_mi_dit_load_lora", "ace_mi_dit_set_lora_scale", "ace_mi_dit_unload_lora",
     "ace_mi_dit_lora_info",
@@ -48,7 +48,7 @@ EXPORTED_SYMBOLS = (
 
 # Every symbol declared in include/acestep_mi355x_selftest.h: the TEST library (libacestep_mi355x_selftest.so = the
 # product objects + the kernel self-test / micro-benchmark entries); the product library does not export them.
-SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_bench_attention", "ace_mi_bench_gemm",
+SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_kernel_attn_probs", "ace_mi_bench_attention", "ace_mi_bench_gemm",
                     "ace_mi_kernel_gemm_q", "ace_mi_kernel_dequant", "ace_mi_bench_gemm_q", "ace_mi_kernel_gemm_a8",
                     "ace_mi_kernel_gemm_a8_mode", "ace_mi_kernel_attn_kh", "ace_mi_kernel_lora_merge",
                     "ace_mi_kernel_dequant_blocks", "ace_mi_kernel_dequant_segments", "ace_mi_bench_dequant_blocks",
@@ -183,6 +183,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.ace_mi_dit_weight_desc.restype = ctypes.c_int
     lib.ace_mi_dit_forward_batched.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     lib.ace_mi_dit_forward_batched.restype = ctypes.c_int
+    lib.ace_mi_dit_forward_capture.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, ip, ip, i32, vp, vp, vp]
+    lib.ace_mi_dit_forward_capture.restype = ctypes.c_int
     lib.ace_mi_dit_sample.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, fp, i32, vp]
     lib.ace_mi_dit_sample.restype = ctypes.c_int
     lib.ace_mi_dit_sample_ex.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, fp, i32, i32, vp, i32, vp, vp, i32, vp]
@@ -323,6 +325,7 @@ def load_selftest_library() -> ctypes.CDLL:
     lib.ace_mi_kernel_gemm.restype = ctypes.c_int
     lib.ace_mi_kernel_attention.argtypes = [i32, i32, i32, i32, i32, i32, f32, i32, fp, fp, ip, fp]
     lib.ace_mi_kernel_attention.restype = ctypes.c_int
+    _bind_attn_probs(lib)
     lib.ace_mi_bench_gemm.argtypes = [i32, i32, i32, i32, i32, i32, i32, fp]
     lib.ace_mi_bench_attention.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, fp]
     lib.ace_mi_bench_attention.restype = ctypes.c_int
@@ -381,6 +384,7 @@ class GGMLCAPIBridge:
         self._ensure_ok(st, "ace_ggml_create")
         atexit.register(self.close)
         self.info: Optional[AceMiDitInfo] = None
+        self.host_memory = False  # True: the library's "device" pointers are host pointers (a host build of the runtime)
         self.audio_channels = 0
         self.hop_length = 0
         self.latent_channels = 0
@@ -755,6 +759,19 @@ class GGMLCAPIBridge:
                                                  int(enc_len), d_t, d_r, d_out, stream or None)
         self._ensure_ok(st, "ace_mi_dit_forward_batched")
 
+    def dit_forward_capture_device(self, batch: int, seq_len: int, enc_len: int, d_hidden: int, d_context: int,
+                                   d_enc: int, d_mask: int, d_enc_mask: int, d_t: int, d_r: int, pairs, early_exit: bool,
+                                   d_out: int, d_probs: int, stream: int = 0) -> None:
+        """ace_mi_dit_forward_capture: pairs = [(layer, head), ...]; d_probs device f32 [len(pairs)][batch][Np][enc_len]
+        in that order; d_out may be 0 with early_exit."""
+        layers = np.ascontiguousarray([int(p[0]) for p in pairs], dtype=np.int32)
+        heads = np.ascontiguousarray([int(p[1]) for p in pairs], dtype=np.int32)
+        st = self.lib.ace_mi_dit_forward_capture(self.ctx, int(batch), int(seq_len), int(enc_len), d_hidden or None,
+                                                 d_context or None, d_enc or None, d_mask or None, d_enc_mask or None,
+                                                 d_t, d_r, len(layers), _iptr(layers), _iptr(heads),
+                                                 1 if early_exit else 0, d_out or None, d_probs or None, stream or None)
+        self._ensure_ok(st, "ace_mi_dit_forward_capture")
+
     def dit_sample_device(self, batch: int, seq_len: int, enc_len: int, d_xt: int, d_context: int, d_enc: int,
                           d_mask: int, d_enc_mask: int, schedule: List[float], stream: int = 0) -> None:
         sched = np.ascontiguousarray(schedule, dtype=np.float32)
@@ -876,6 +893,36 @@ def kernel_attention(q: np.ndarray, kv: np.ndarray, hq: int, hkv: int, window: i
                                      _iptr(km), _fptr(out))
     if st != ACE_GGML_OK:
         raise RuntimeError(f"ace_mi_kernel_attention failed (status={st})")
+    return out
+
+
+def _bind_attn_probs(lib):
+    i32, fp, ip = ctypes.c_int32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int32)
+    lib.ace_mi_kernel_attn_probs.argtypes = [i32, i32, i32, i32, i32, ctypes.c_float, fp, fp, ip, i32, ip, fp]
+    lib.ace_mi_kernel_attn_probs.restype = ctypes.c_int
+    return lib
+
+
+def kernel_attn_probs(q: np.ndarray, k: np.ndarray, hq: int, hkv: int, heads, kmask: Optional[np.ndarray] = None,
+                      scale: Optional[float] = None, out0: Optional[np.ndarray] = None, lib=None) -> np.ndarray:
+    """One launch_attn_probs: q [B][nq][hq*128] f32, k [B][nk][hkv*128] f32 (the kernel reads their fp16 roundings),
+    kmask [B][nk] int32 or None, heads = the listed query heads -> f32 [len(heads)][B][nq][nk].  out0: the output
+    array's contents before the launch (sentinels; default NaN).  The entry fails when the launch wrote outside the
+    output.  `lib`: a loaded library that exports the entry (default: the GPU self-test library)."""
+    lib = _bind_attn_probs(lib) if lib is not None else load_selftest_library()
+    q = np.ascontiguousarray(q, dtype=np.float32)
+    k = np.ascontiguousarray(k, dtype=np.float32)
+    B, nq, _ = q.shape
+    nk = k.shape[1]
+    hd = np.ascontiguousarray(heads, dtype=np.int32)
+    km = None if kmask is None else np.ascontiguousarray(kmask, dtype=np.int32)
+    shape = (len(hd), B, nq, nk)
+    out = np.full(shape, np.nan, np.float32) if out0 is None else np.ascontiguousarray(out0, dtype=np.float32).copy()
+    assert out.shape == shape, (out.shape, shape)
+    sc = float(scale) if scale is not None else 1.0 / np.sqrt(128.0)
+    st = lib.ace_mi_kernel_attn_probs(B, hq, hkv, nq, nk, sc, _fptr(q), _fptr(k), _iptr(km), len(hd), _iptr(hd), _fptr(out))
+    if st != ACE_GGML_OK:
+        raise RuntimeError(f"ace_mi_kernel_attn_probs failed (status={st})")
     return out
 
 

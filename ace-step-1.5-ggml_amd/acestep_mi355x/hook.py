@@ -4,7 +4,8 @@ Mirrors `_install_ggml_dit_backend` (scripts/run_non_ggml_real_case.py:445-538):
 replaces `dit_handler.model.decoder.forward` with a function of the same keyword
 signature (hidden_states, timestep, timestep_r, attention_mask,
 encoder_hidden_states, encoder_attention_mask, context_latents, use_cache,
-past_key_values, ..., output_attentions) returning `(pred, past_key_values[, None])`,
+past_key_values, ..., output_attentions) returning `(pred, past_key_values[, None])`
+(or the cross-attention maps in place of `None` when a `custom_layers_config` selects heads),
 and marks the handler with `_ggml_dit_backend` / `_ggml_dit_decoder_forward_hooked`
 (read by acestep/handler.py:2740-2746).
 
@@ -82,8 +83,73 @@ def dit_forward_torch(bridge, hidden_states, timestep, timestep_r, attention_mas
     return torch.from_numpy(out_np).to(dev).to(hidden_states.dtype)
 
 
+def dit_capture_torch(bridge, hidden_states, timestep, timestep_r, attention_mask, encoder_hidden_states,
+                      encoder_attention_mask, context_latents, layers_config, early_exit: bool):
+    """One DiT step that also returns the cross-attention maps of `layers_config` = {layer: [heads]} (what the reference
+    decoder returns under output_attentions=True with a custom_layers_config; acestep/handler.py get_lyric_timestamp /
+    get_lyric_score read it).  Returns (pred, attentions): attentions is a tuple of max(layer) + 1 tensors
+    [B, Hq, Np, L] in hidden_states' dtype on its device -- a selected layer holds the captured heads (every other
+    head zero), an unselected layer is a stride-0 view of one zero.  With early_exit the walk stops at the last
+    selected layer and pred is zeros.  The tensors are handed over as pointers on torch's current stream
+    (ace_mi_dit_forward_capture, <= 8 items per call); host tensors are moved to the bridge's GPU and the results back
+    (a bridge whose library computes in host memory says so with `host_memory = True`)."""
+    import torch
+
+    pairs = [(int(layer), int(h)) for layer in sorted(layers_config) for h in layers_config[layer]]
+    if not pairs:
+        raise ValueError("custom_layers_config selects no head")
+    hs = hidden_states.detach()
+    bsz, seq_len, audio = hs.shape
+    home = hs.device
+    info = bridge.info
+    dev = home
+    if home.type != "cuda" and not getattr(bridge, "host_memory", False):  # host tensors: computed on the GPU
+        dev = torch.device("cuda", max(0, int(info.device)))
+    ctx = context_latents.detach().to(device=dev, dtype=torch.float32).contiguous()
+    enc = encoder_hidden_states.detach().to(device=dev, dtype=torch.float32).contiguous()
+    x = hs.to(device=dev, dtype=torch.float32).contiguous()
+    enc_len = int(enc.shape[1])
+    am = _mask(attention_mask, (bsz, seq_len), dev, torch)
+    eam = _mask(encoder_attention_mask, (bsz, enc_len), dev, torch)
+    t = _timesteps(timestep, bsz, dev, torch)
+    r = _timesteps(timestep_r, bsz, dev, torch)
+    n_heads, patch = int(info.num_heads), int(info.patch_size)
+    n_patch = (seq_len + patch - 1) // patch
+    out = torch.zeros((bsz, seq_len, audio), dtype=torch.float32, device=dev)
+    probs = torch.empty((bsz, len(pairs), n_patch, enc_len), dtype=torch.float32, device=dev)
+    with _OrderedCall(bridge, dev) as stream:
+        for b0 in range(0, bsz, MAX_BATCH_PER_CALL):
+            b1 = min(bsz, b0 + MAX_BATCH_PER_CALL)
+            n = b1 - b0
+            chunk = torch.empty((len(pairs), n, n_patch, enc_len), dtype=torch.float32, device=dev)
+            bridge.dit_forward_capture_device(
+                n, seq_len, enc_len, x[b0:b1].data_ptr(), ctx[b0:b1].data_ptr(), enc[b0:b1].data_ptr(),
+                am[b0:b1].data_ptr() if am is not None else 0, eam[b0:b1].data_ptr() if eam is not None else 0,
+                t[b0:b1].data_ptr(), r[b0:b1].data_ptr(), pairs, bool(early_exit),
+                0 if early_exit else out[b0:b1].data_ptr(), chunk.data_ptr(), stream)
+            probs[b0:b1] = chunk.transpose(0, 1)
+    dtype = hidden_states.dtype
+    out, probs = out.to(home), probs.to(home)
+    dev = home
+    zero = torch.zeros((), dtype=dtype, device=dev)
+    attentions = []
+    for layer in range(max(layers_config) + 1):
+        idx = [j for j, p in enumerate(pairs) if p[0] == layer]
+        if not idx:
+            attentions.append(zero.expand(bsz, n_heads, n_patch, enc_len))  # stride 0: no memory
+            continue
+        full = torch.zeros((bsz, n_heads, n_patch, enc_len), dtype=dtype, device=dev)
+        full[:, [pairs[j][1] for j in idx]] = probs[:, idx].to(dtype)
+        attentions.append(full)
+    return out.to(dtype), tuple(attentions)
+
+
 def install_dit_backend(dit_handler: Any, bridge) -> None:
-    """Replace dit_handler.model.decoder.forward with the MI355X engine."""
+    """Replace dit_handler.model.decoder.forward with the MI355X engine.
+
+    output_attentions=True with a non-empty custom_layers_config dict (and a bridge that has
+    dit_forward_capture_device) returns the cross-attention maps as outputs[2] (dit_capture_torch), so the handler's
+    get_lyric_timestamp / get_lyric_score work unmodified; in every other case outputs[2] is None."""
     decoder = dit_handler.model.decoder
     original_forward = decoder.forward
 
@@ -101,6 +167,12 @@ def install_dit_backend(dit_handler: Any, bridge) -> None:
                                     output_attentions=output_attentions, return_hidden_states=return_hidden_states,
                                     custom_layers_config=custom_layers_config,
                                     enable_early_exit=enable_early_exit, **flash_attn_kwargs)
+        if (output_attentions and isinstance(custom_layers_config, dict) and custom_layers_config
+                and hasattr(bridge, "dit_forward_capture_device")):
+            pred, attentions = dit_capture_torch(bridge, hidden_states, timestep, timestep_r, attention_mask,
+                                                 encoder_hidden_states, encoder_attention_mask, context_latents,
+                                                 custom_layers_config, bool(enable_early_exit))
+            return (pred, past_key_values, attentions)
         pred = dit_forward_torch(bridge, hidden_states, timestep, timestep_r, attention_mask, encoder_hidden_states,
                                  encoder_attention_mask, context_latents)
         outputs = (pred, past_key_values)

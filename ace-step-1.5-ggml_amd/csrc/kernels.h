@@ -292,6 +292,30 @@ inline AttnPrecision attn_precision_from_env(AttnPrecision dflt) {
 }
 void launch_attention(ActType out_t, const AttnArgs& a, hipStream_t s);
 
+// ------------------------------------------------------------ attention probabilities (kernels/attn_probs.hip)
+// The softmax the flash kernels never materialise, for a list of query heads (the lyric-alignment features read the
+// cross-attention maps): for every listed head h, with its KV head h / (Hq / Hkv),
+//   out[i][b][q][k] = exp(s - max_k s) / sum_k exp(s - max_k s),  s = scale * (q . k) + kbias[b][k],  h = heads[i],
+// from the fp16 HI planes of the Q / K images of AttnArgs alone (the lo planes, which hold fp8 bytes in the f8c mode,
+// are not read): fp16-operand precision, f32 accumulate.  out is dense f32 [n_heads][B][nq][nk]; a masked key
+// (kbias -inf, or k >= nk) is exactly +0, a row without an unmasked key is all zeros (not NaN).  The list may repeat
+// a head and be in any order.  nq_pad % 128 == 0, nk_pad % 64 == 0.  Fixed reduction order: bit-identical between runs.
+constexpr int ATTN_PROBS_MAX_HEADS = 32;  // per launch; a longer list takes several launches
+struct AttnProbArgs {
+    const uint16_t* q = nullptr;   // [B][Hq][nq_pad][128]
+    const uint16_t* k = nullptr;   // [B][Hkv][nk_pad][128]
+    const float* kbias = nullptr;  // [B][nk_pad] additive (0 / -inf) or null
+    int B = 0, Hq = 0, Hkv = 0;
+    int nq = 0, nq_pad = 0, nk = 0, nk_pad = 0;
+    float scale = 0.f;
+    int n_heads = 0;
+    const int* heads = nullptr;  // host array [n_heads]: passed to the kernel by value
+    const int* slots = nullptr;  // host array [n_heads] or null: listed head i writes out[slots[i]] instead of out[i]
+                                 // (out then holds max(slots) + 1 maps; two entries may not share a slot)
+    float* out = nullptr;
+};
+void launch_attn_probs(const AttnProbArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------ elementwise
 // Pack [context | hidden] frames into patches: out act [B*Np][P*Cin].
 // x3: write the f32 value as the fp16 triple [hi | hi | lo] per row (input of a WF_F32X3 weight).

@@ -234,6 +234,63 @@ ace_ggml_status ace_mi_dit_forward_batched(ace_ggml_context* ctx, int32_t batch,
     return ACE_GGML_OK;
 }
 
+ace_ggml_status ace_mi_dit_forward_capture(ace_ggml_context* ctx, int32_t batch, int32_t seq_len, int32_t enc_len,
+                                           const float* d_hidden, const float* d_context, const float* d_enc,
+                                           const int32_t* d_mask, const int32_t* d_enc_mask, const float* d_timestep,
+                                           const float* d_timestep_r, int32_t n_pairs, const int32_t* layers,
+                                           const int32_t* heads, int32_t early_exit, float* d_out, float* d_probs,
+                                           void* stream) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    if (seq_len <= 0 || batch <= 0 || !d_timestep || !d_timestep_r)
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "bad batch, seq_len or timestep pointers");
+    if (!ctx->dit) return set_error(ctx, ACE_GGML_ERR, "dit not loaded");
+    const acemi::DitConfig& c = ctx->dit->model().cfg;
+    auto bad = [&](const std::string& msg) { return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, msg); };
+    if (n_pairs < 1) return bad("capture: n_pairs = " + std::to_string(n_pairs) + " (must be >= 1)");
+    if (!layers || !heads) return bad("capture: null layers / heads");
+    if (enc_len <= 0) return bad("capture: enc_len = " + std::to_string(enc_len) + " (must be > 0)");
+    if (!d_enc) return bad("encoder_hidden_states is null");
+    if (!d_probs) return bad("capture: probs is null");
+    if (!early_exit && !d_out) return bad("capture: out is null without early_exit");
+    for (int j = 0; j < n_pairs; ++j) {
+        if (layers[j] < 0 || layers[j] >= c.layers)
+            return bad("capture: layer " + std::to_string(layers[j]) + " is outside [0, " + std::to_string(c.layers) +
+                       ")");
+        if (heads[j] < 0 || heads[j] >= c.hq)
+            return bad("capture: head " + std::to_string(heads[j]) + " is outside [0, " + std::to_string(c.hq) + ")");
+        if (!ctx->dit->model().layers[layers[j]].cross)
+            return bad("capture: layer " + std::to_string(layers[j]) + " has no cross-attention block");
+    }
+    try {
+        bind_device(ctx);
+        acemi::gemm_splitk_check();  // a failure of an earlier asynchronous call surfaces here
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+        acemi::ForwardIO io;
+        io.B = batch;
+        io.T = seq_len;
+        io.L = enc_len;
+        io.hidden = d_hidden;
+        io.context = d_context;
+        io.enc = d_enc;
+        io.mask = d_mask;
+        io.enc_mask = d_enc_mask;
+        io.t = d_timestep;
+        io.r = d_timestep_r;
+        io.out = d_out;
+        io.max_layers = max_layers_env();
+        const std::vector<int> ls(layers, layers + n_pairs), hs(heads, heads + n_pairs);
+        io.n_pairs = n_pairs;
+        io.layers = ls.data();
+        io.heads = hs.data();
+        io.probs = d_probs;
+        io.early_exit = early_exit != 0;
+        ctx->dit->forward(io, s);
+    } catch (const std::exception& e) {
+        return set_error(ctx, ACE_GGML_ERR, std::string("dit forward failed: ") + e.what());
+    }
+    return ACE_GGML_OK;
+}
+
 namespace {
 // The generation loop shared by ace_mi_dit_sample (the C sampler, acestep_ggml.cpp:2042-2086) and
 // ace_mi_dit_sample_ex (the Python/MLX loop, acestep/mlx_dit/generate.py:143-199).

@@ -11,6 +11,7 @@
 #include <tuple>
 #include <type_traits>
 
+#include "../kernels/attn_probs_host.h"  // empty under hipcc; the host build's launch_attn_probs
 #include "lora.h"
 #include "operands.h"
 
@@ -230,6 +231,26 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
 
     int n_layers = c.layers;
     if (io.max_layers > 0) n_layers = std::min(n_layers, io.max_layers);
+    // capture request: every listed layer must run and own a cross block; an early exit ends the walk at the last one
+    const bool capture = io.n_pairs > 0;
+    const bool early_exit = capture && io.early_exit;
+    if (capture) {
+        ACEMI_CHECK(io.layers && io.heads && io.probs, "capture: null layers / heads / probs");
+        ACEMI_CHECK(L > 0, "capture: enc_len must be > 0");
+        int last = 0;
+        for (int j = 0; j < io.n_pairs; ++j) {
+            ACEMI_CHECK(io.layers[j] >= 0 && io.layers[j] < n_layers,
+                        "capture: layer " + std::to_string(io.layers[j]) + " is outside the " +
+                            std::to_string(n_layers) + " layers this forward runs");
+            ACEMI_CHECK(m.layers[io.layers[j]].cross,
+                        "capture: layer " + std::to_string(io.layers[j]) + " has no cross-attention block");
+            ACEMI_CHECK(io.heads[j] >= 0 && io.heads[j] < c.hq,
+                        "capture: head " + std::to_string(io.heads[j]) + " is outside [0, " + std::to_string(c.hq) + ")");
+            last = std::max(last, io.layers[j]);
+        }
+        if (early_exit) n_layers = last + 1;
+    }
+    ACEMI_CHECK(early_exit || io.out != nullptr, "output buffer is null");
     // the product reads weight images (weight_images.h); parity multiplies the resident weights: nothing staged
     images_.begin_forward(QACT ? 0 : n_layers, io.reuse_stage, s);
     const int Kin = kin * P * c.in_channels;
@@ -362,6 +383,7 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
 
     const float* mods = get<float>(mods_);
     const int64_t mstride = 6LL * H;  // per item within a layer
+    std::vector<int> cap_heads, cap_slots;  // capture: one layer's heads and their places in io.probs
 
     for (int li = 0; li < n_layers; ++li) {  // :1466-1535
         const DevLayer& ly = m.layers[li];
@@ -394,6 +416,25 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
         if (ly.cross && L > 0) {
             norm(at, ly.cross_norm, nullptr, nullptr, 0, act, false);
             project(lw[BW_CQ], qd, cross_q_prep(dims, planes, ly.cq_norm, get<uint16_t>(qh_)), "gemm_cross_q");
+            if (capture) {  // this layer's pairs in one launch: qh_ holds its cross queries until the next layer's QKV
+                cap_heads.clear();
+                cap_slots.clear();
+                for (int j = 0; j < io.n_pairs; ++j)
+                    if (io.layers[j] == li) {
+                        cap_heads.push_back(io.heads[j]);
+                        cap_slots.push_back(j);
+                    }
+                if (!cap_heads.empty()) {
+                    tic(s);
+                    launch_attn_probs(attn_prob_args(dims, get<uint16_t>(qh_), get<uint16_t>(kc_) + li * kc_layer,
+                                                     io.enc_mask ? get<float>(kbias_c_) : nullptr, L, Lpad,
+                                                     (int)cap_heads.size(), cap_heads.data(), cap_slots.data(),
+                                                     io.probs),
+                                      s);
+                    toc("attn_probs", s);
+                }
+                if (early_exit && li + 1 == n_layers) break;  // nothing after the last capture is read
+            }
             attention(get<uint16_t>(kc_) + li * kc_layer, get<uint16_t>(vc_) + li * kc_layer,
                       io.enc_mask ? get<float>(kbias_c_) : nullptr, L, Lpad, kc_plane, 0, "attn_cross");
             linear(attn, qd, M, lw[BW_CO], H, qd, epi_resid(x, H), "gemm_cross_o");
@@ -406,7 +447,7 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
     }
 
     // ---- output head (:1537-1559)
-    {
+    if (!early_exit) {
         const float* om = get<float>(outmod_);
         Row* head_in = kout == 3 ? act2 : act;  // act2_ is sized for M x 3H too
         norm(m.proj_out_w.act(), m.norm_out, om + H, om, 2LL * H, head_in, kout == 3);

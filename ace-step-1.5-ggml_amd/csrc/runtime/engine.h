@@ -47,6 +47,16 @@ struct ForwardIO {
     const float* ts_proj = nullptr;
     const float* ts_temb_t = nullptr;
     const float* ts_temb_r = nullptr;
+    // Capture request (ace_mi_dit_forward_capture): the cross-attention probabilities softmax(q k^T scale + mask) of
+    // n_pairs (layer, head) pairs, written to probs [n_pairs][B][Np][L] f32 (device) in the caller's pair order
+    // (launch_attn_probs on the fp16 hi planes the cross attention reads; duplicates allowed, every listed layer must
+    // run and have a cross block).  early_exit: the walk stops at the last listed layer's capture and writes no `out`
+    // (which may be null).  n_pairs == 0: exactly the launches of a forward without this block.
+    int n_pairs = 0;
+    const int* layers = nullptr;  // host [n_pairs]
+    const int* heads = nullptr;   // host [n_pairs]
+    float* probs = nullptr;
+    bool early_exit = false;
 };
 
 // One condition-encoder pass for B items of n tokens each (forward_lyric_encoder /

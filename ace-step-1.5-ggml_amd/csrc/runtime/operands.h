@@ -141,6 +141,29 @@ inline AttnArgs attn_args(const AttnDims& d, AttnPlanes p, const uint16_t* q, co
     return aa;
 }
 
+// The probabilities of n_heads listed heads of d's queries (q) over nk keys in k (launch_attn_probs: the hi planes
+// only), head i into map slots[i] of out.
+inline AttnProbArgs attn_prob_args(const AttnDims& d, const uint16_t* q, const uint16_t* k, const float* kbias, int nk,
+                                   int nk_pad, int n_heads, const int* heads, const int* slots, float* out) {
+    AttnProbArgs pa{};
+    pa.q = q;
+    pa.k = k;
+    pa.kbias = kbias;
+    pa.B = d.B;
+    pa.Hq = d.hq;
+    pa.Hkv = d.hkv;
+    pa.nq = d.n;
+    pa.nq_pad = d.n_pad;
+    pa.nk = nk;
+    pa.nk_pad = nk_pad;
+    pa.scale = 1.0f / std::sqrt((float)d.D);
+    pa.n_heads = n_heads;
+    pa.heads = heads;
+    pa.slots = slots;
+    pa.out = out;
+    return pa;
+}
+
 // ---- the GEMM epilogues of the walks (GemmEpiKind)
 inline GemmEpilogue epi_store_f32(float* c, int ldc, const float* bias = nullptr) {
     GemmEpilogue e;

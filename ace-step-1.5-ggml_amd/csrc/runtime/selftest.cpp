@@ -188,6 +188,88 @@ ace_ggml_status ace_mi_kernel_attention(int32_t B, int32_t Hq, int32_t Hkv, int3
     return ACE_GGML_OK;
 }
 
+// Attention probabilities of the listed heads (kernels/attn_probs.hip): operands through the engine's prep kernel as
+// above (no norm, no RoPE; the kernel reads the fp16 hi planes), one launch.  The device output sits between two
+// guard runs of NaN-pattern words that the launch must leave alone.
+ace_ggml_status ace_mi_kernel_attn_probs(int32_t B, int32_t Hq, int32_t Hkv, int32_t nq, int32_t nk, float scale,
+                                         const float* q, const float* k, const int32_t* kmask, int32_t n_heads,
+                                         const int32_t* heads, float* out) {
+    using namespace acemi;
+    if (B <= 0 || Hq <= 0 || Hkv <= 0 || Hq % Hkv != 0 || nq <= 0 || nk <= 0 || !q || !k || n_heads <= 0 || !heads ||
+        !out)
+        return ACE_GGML_ERR_INVALID_ARG;
+    for (int i = 0; i < n_heads; ++i)
+        if (heads[i] < 0 || heads[i] >= Hq) return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const int D = 128, G = 1024;
+        const int nq_pad = (int)round_up(nq, 128), nk_pad = (int)round_up(nk, 64);
+        const size_t nqf = (size_t)B * nq * Hq * D, nkf = (size_t)B * nk * Hkv * D;
+        const size_t n_out = (size_t)n_heads * B * nq * nk;
+        DevMem dq(nqf * 4), dk(nkf * 4), dm((size_t)B * nk * 4), dqh((size_t)B * Hq * nq_pad * D * 2),
+            dkh((size_t)B * Hkv * nk_pad * D * 2), dkb((size_t)B * nk_pad * 4), dout((n_out + 2 * G) * 4);
+        ACEMI_HIP(hipMemcpy(dq.p, q, nqf * 4, hipMemcpyHostToDevice));
+        ACEMI_HIP(hipMemcpy(dk.p, k, nkf * 4, hipMemcpyHostToDevice));
+        if (kmask) ACEMI_HIP(hipMemcpy(dm.p, kmask, (size_t)B * nk * 4, hipMemcpyHostToDevice));
+        std::vector<uint32_t> guard((size_t)G, 0x7fc0a11cu);
+        ACEMI_HIP(hipMemcpy(dout.as<float>(), guard.data(), (size_t)G * 4, hipMemcpyHostToDevice));
+        ACEMI_HIP(hipMemcpy(dout.as<float>() + G, out, n_out * 4, hipMemcpyHostToDevice));
+        ACEMI_HIP(hipMemcpy(dout.as<float>() + G + n_out, guard.data(), (size_t)G * 4, hipMemcpyHostToDevice));
+        PrepArgs pq{};
+        pq.src = dq.as<float>();
+        pq.ld = Hq * D;
+        pq.q_col = 0;
+        pq.k_col = -1;
+        pq.v_col = -1;
+        pq.hq = Hq;
+        pq.hkv = Hkv;
+        pq.n_tok = nq;
+        pq.n_pad = nq_pad;
+        pq.B = B;
+        pq.qh = dqh.as<uint16_t>();
+        launch_attn_prep(pq, nullptr);
+        PrepArgs pk{};
+        pk.src = dk.as<float>();
+        pk.ld = Hkv * D;
+        pk.q_col = -1;
+        pk.k_col = 0;
+        pk.v_col = -1;
+        pk.hq = Hq;
+        pk.hkv = Hkv;
+        pk.n_tok = nk;
+        pk.n_pad = nk_pad;
+        pk.B = B;
+        pk.kh = dkh.as<uint16_t>();
+        launch_attn_prep(pk, nullptr);
+        launch_key_bias(kmask ? dm.as<int32_t>() : nullptr, B, nk, 1, nk, nk_pad, dkb.as<float>(), nullptr);
+        AttnProbArgs a{};
+        a.q = dqh.as<uint16_t>();
+        a.k = dkh.as<uint16_t>();
+        a.kbias = kmask ? dkb.as<float>() : nullptr;
+        a.B = B;
+        a.Hq = Hq;
+        a.Hkv = Hkv;
+        a.nq = nq;
+        a.nq_pad = nq_pad;
+        a.nk = nk;
+        a.nk_pad = nk_pad;
+        a.scale = scale;
+        a.n_heads = n_heads;
+        a.heads = heads;
+        a.out = dout.as<float>() + G;
+        launch_attn_probs(a, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        std::vector<uint32_t> g0((size_t)G), g1((size_t)G);
+        ACEMI_HIP(hipMemcpy(g0.data(), dout.as<float>(), (size_t)G * 4, hipMemcpyDeviceToHost));
+        ACEMI_HIP(hipMemcpy(out, dout.as<float>() + G, n_out * 4, hipMemcpyDeviceToHost));
+        ACEMI_HIP(hipMemcpy(g1.data(), dout.as<float>() + G + n_out, (size_t)G * 4, hipMemcpyDeviceToHost));
+        if (g0 != guard || g1 != guard) throw std::runtime_error("a guard word outside the output was written");
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_attn_probs: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
 // Attention micro-benchmark: pseudo-random N(0,1)-like q / kv (fixed seed), average ms per launch over
 // `iters` launches timed with hipEvents.  flags: bit 0 split (hi/lo) operands, bit 1 causal, bit 3 hi/lo P.V,
 // bit 2 a key-padding mask (every 7th key masked), bit 4 the fp8 correction encoding (with bit 3: with bit 0 the f8c

@@ -59,6 +59,25 @@ ACE_GGML_API ace_ggml_status ace_mi_dit_forward_batched(ace_ggml_context* ctx, i
                                                         int32_t seq_len, int32_t enc_len, const float* d_timestep,
                                                         const float* d_timestep_r, float* d_out, void* stream);
 
+/* ace_mi_dit_forward_batched that also returns cross-attention probabilities (what the reference decoder returns
+ * under output_attentions=True with a custom_layers_config; read by get_lyric_timestamp / get_lyric_score):
+ * `layers` / `heads` are HOST arrays of n_pairs (layer, head) pairs, d_probs is DEVICE f32
+ * [n_pairs][batch][ceil(seq_len / patch)][enc_len] in the caller's pair order, each map
+ * softmax(q k^T / sqrt(head_dim) + encoder mask) over the encoder tokens at fp16 operand precision (a masked token is
+ * exactly 0, an item whose tokens are all masked is all zeros).  Duplicate pairs are allowed.  early_exit != 0 stops
+ * after the last listed layer: d_out is not written and may be NULL.  With early_exit == 0 d_out is bit-identical to
+ * ace_mi_dit_forward_batched on the same inputs.  ACE_GGML_ERR_INVALID_ARG with a message naming the value for
+ * n_pairs < 1, a layer outside [0, layers), a head outside [0, heads), a layer without a cross-attention block,
+ * enc_len <= 0 and a NULL d_probs.  The call leaves no state behind. */
+ACE_GGML_API ace_ggml_status ace_mi_dit_forward_capture(ace_ggml_context* ctx, int32_t batch, int32_t seq_len,
+                                                        int32_t enc_len, const float* d_hidden,
+                                                        const float* d_context, const float* d_enc,
+                                                        const int32_t* d_mask, const int32_t* d_enc_mask,
+                                                        const float* d_timestep, const float* d_timestep_r,
+                                                        int32_t n_pairs, const int32_t* layers, const int32_t* heads,
+                                                        int32_t early_exit, float* d_out, float* d_probs,
+                                                        void* stream);
+
 /* Euler ODE sampling on the device (acestep_ggml.cpp:2056-2086, mlx_dit/generate.py:154-197):
  * for i in steps: v = DiT(xt, t_i, r = t_i); xt -= v * (t_i - t_{i+1}); last step xt -= v * t_i.
  * d_xt [B][T][audio] holds the initial noise on entry and x0 on return.

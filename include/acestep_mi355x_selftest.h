@@ -27,6 +27,16 @@ ACE_GGML_API ace_ggml_status ace_mi_kernel_gemm(int32_t act_type, int32_t epi, i
 ACE_GGML_API ace_ggml_status ace_mi_kernel_attention(int32_t B, int32_t Hq, int32_t Hkv, int32_t nq, int32_t nk,
                                                      int32_t window, float scale, int32_t split, const float* q,
                                                      const float* kv, const int32_t* kmask, float* out);
+/* Attention probabilities of the listed query heads (kernels/attn_probs.hip, one launch; no norm / RoPE): q
+ * [B][nq][Hq*128] f32, k [B][nk][Hkv*128] f32, prepared as ace_mi_kernel_attention prepares its operands (the kernel
+ * reads their fp16 roundings), kmask [B][nk] int32 or NULL, heads [n_heads] query heads (any order, repeats allowed).
+ * out f32 [n_heads][B][nq][nk] is copied to the device before the launch and back after it, so a caller's sentinels
+ * show an element the kernel did not write; the device buffer carries 1024 guard floats on either side of the payload,
+ * and ACE_GGML_ERR is returned when the launch changed one of them. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_attn_probs(int32_t B, int32_t Hq, int32_t Hkv, int32_t nq, int32_t nk,
+                                                      float scale, const float* q, const float* k,
+                                                      const int32_t* kmask, int32_t n_heads, const int32_t* heads,
+                                                      float* out);
 
 /* Attention micro-benchmark on pseudo-random device operands (fixed seed): average ms per launch (HIP
  * events) of the engine's attention kernel; flags bit 0 = hi/lo operands, bit 1 = causal, bit 2 = a
