@@ -53,6 +53,7 @@ SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_ker
                     "ace_mi_kernel_gemm_a8_mode", "ace_mi_kernel_attn_kh", "ace_mi_kernel_lora_merge",
                     "ace_mi_kernel_dequant_blocks", "ace_mi_kernel_dequant_segments", "ace_mi_bench_dequant_blocks",
                     "ace_mi_gemm_resolve", "ace_mi_gemm_variant_row", "ace_mi_gemm_variant_arg_ok",
+                    "ace_mi_kernel_attn_policy", "ace_mi_attn_plan", "ace_mi_attn_plan_block", "ace_mi_attn_plan_tiles",
                     "ace_mi_kernel_lm_skinny", "ace_mi_kernel_lm_embed", "ace_mi_kernel_lm_qkv_post",
                     "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention", "ace_mi_kernel_lm_skinny_q",
                     "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_select",
@@ -299,6 +300,19 @@ def _bind_gemm_variants(lib: ctypes.CDLL) -> ctypes.CDLL:
     return lib
 
 
+def _bind_attn_plan(lib: ctypes.CDLL) -> ctypes.CDLL:
+    i32, ip = ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)
+    lib.ace_mi_kernel_attn_policy.argtypes = [ip]
+    lib.ace_mi_kernel_attn_policy.restype = ctypes.c_int
+    lib.ace_mi_attn_plan.argtypes = [ip, ip, ip]
+    lib.ace_mi_attn_plan.restype = ctypes.c_int
+    lib.ace_mi_attn_plan_block.argtypes = [i32, i32, i32, i32, i32, ip]
+    lib.ace_mi_attn_plan_block.restype = ctypes.c_int
+    lib.ace_mi_attn_plan_tiles.argtypes = [i32, i32, i32, i32, i32, i32, i32, ip]
+    lib.ace_mi_attn_plan_tiles.restype = ctypes.c_int
+    return lib
+
+
 def selftest_library_path() -> str:
     """Path of the TEST library (a superset of the product ABI that also reads the test-only environment hooks,
     runtime/test_hooks.cpp)."""
@@ -349,6 +363,7 @@ def load_selftest_library() -> ctypes.CDLL:
     lib.ace_mi_bench_dequant_blocks.argtypes = [i32, i32, i32, i32, i32, fp]
     lib.ace_mi_bench_dequant_blocks.restype = ctypes.c_int
     _bind_gemm_variants(lib)
+    _bind_attn_plan(lib)
     _bind_lm_kernels(lib)
     _bind_vae_kernels(lib)
     _SELFTEST = lib
@@ -1487,6 +1502,63 @@ def kernel_attn_kh(mode: int) -> None:
     """f8c attention kernel of this process: -1 environment / default policy, 0 attn2 (one wave per SIMD), 1 attn_kh."""
     if load_selftest_library().ace_mi_kernel_attn_kh(int(mode)) != ACE_GGML_OK:
         raise ValueError(mode)
+
+
+ATTN_SHAPE_FIELDS = ("B", "Hq", "Hkv", "nq", "nk", "window", "causal", "has_part", "split", "pv_split", "f8", "out_f32")
+ATTN_POLICY_FIELDS = ("ksplit_mode", "tail", "tail_min", "xcd_order", "kh", "n_cu")
+ATTN_POLICY_DEFAULT = dict(ksplit_mode=0, tail=1, tail_min=16, xcd_order=1, kh=-1, n_cu=256)
+ATTN_PLAN_FIELDS = ("ksplit", "split_from", "xcd_order", "n_blk", "grid", "kernel", "merge", "merge_grid")
+ATTN_KERNELS = ("attn2", "attn_kh")
+ATTN_MERGES = ("none", "uniform2", "uniform4", "tail")
+
+
+def _attn_policy_words(policy: dict, unset: int):
+    bad = set(policy) - set(ATTN_POLICY_FIELDS)
+    if bad:
+        raise ValueError(f"unknown attention policy fields {sorted(bad)}")
+    return (ctypes.c_int32 * 6)(*[int(policy.get(n, unset if unset is not None else ATTN_POLICY_DEFAULT[n]))
+                                  for n in ATTN_POLICY_FIELDS])
+
+
+def kernel_attn_policy(**policy) -> None:
+    """Override the attention launch policy of this process (csrc/attn_plan.h): ksplit_mode, tail, tail_min,
+    xcd_order, kh, n_cu; a field left out (or -1) stays with the environment / the device, no field clears the
+    override."""
+    if load_selftest_library().ace_mi_kernel_attn_policy(_attn_policy_words(policy, -1)) != ACE_GGML_OK:
+        raise ValueError(policy)
+
+
+def attn_plan(shape, lib=None, **policy) -> dict:
+    """The launch plan of an attention shape (ATTN_SHAPE_FIELDS, a dict or a sequence) under a policy (fields left out:
+    ATTN_POLICY_DEFAULT, i.e. the defaults on a 256-CU device): pure, no device.  `lib` as for gemm_resolve."""
+    lib = _bind_attn_plan(lib) if lib is not None else load_selftest_library()
+    if isinstance(shape, dict):
+        shape = [shape[n] for n in ATTN_SHAPE_FIELDS]
+    out = (ctypes.c_int32 * 8)()
+    if lib.ace_mi_attn_plan((ctypes.c_int32 * 12)(*[int(v) for v in shape]), _attn_policy_words(policy, None),
+                            out) != ACE_GGML_OK:
+        raise ValueError((list(shape), policy))
+    plan = dict(zip(ATTN_PLAN_FIELDS, out))
+    plan["kernel"], plan["merge"] = ATTN_KERNELS[plan["kernel"]], ATTN_MERGES[plan["merge"]]
+    return plan
+
+
+def attn_plan_block(ksplit: int, split_from: int, xcd_order: int, n_blk: int, x: int, lib=None):
+    """Launch index x of a plan -> (logical block, key-range part, parts of the block, valid)."""
+    lib = _bind_attn_plan(lib) if lib is not None else load_selftest_library()
+    out = (ctypes.c_int32 * 4)()
+    if lib.ace_mi_attn_plan_block(ksplit, split_from, xcd_order, n_blk, x, out) != ACE_GGML_OK:
+        raise ValueError((ksplit, split_from, xcd_order, n_blk, x))
+    return out[0], out[1], out[2], bool(out[3])
+
+
+def attn_plan_tiles(nk: int, window: int, causal: bool, q0: int, qpb: int, part: int, parts: int, lib=None):
+    """(first key tile, key tiles) of part `part` of `parts` for the queries [q0, q0 + qpb)."""
+    lib = _bind_attn_plan(lib) if lib is not None else load_selftest_library()
+    out = (ctypes.c_int32 * 2)()
+    if lib.ace_mi_attn_plan_tiles(nk, window, int(bool(causal)), q0, qpb, part, parts, out) != ACE_GGML_OK:
+        raise ValueError((nk, window, causal, q0, qpb, part, parts))
+    return out[0], out[1]
 
 
 def kernel_gemm_a8_mode(mode: int) -> None:

@@ -6,6 +6,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "attn_plan.h"
 #include "common.h"
 
 namespace acemi {
@@ -264,9 +265,36 @@ struct AttnArgs {
     bool f8 = false;  // f8c mode (needs split + pv_split): the lo planes hold fp8 hi / lo operands (prep_math.h), the
                       // correction products Kl.Qh + Kh.Ql and Vl.Ph + Vh.Pl run as block-scaled fp8 MFMAs
 };
-size_t attn_part_floats(int B, int nq, int Hq);
-// Which kernel runs the f8c mode: -1 = ACE_MI_ATTN_KH (0 never, 1 always) / default (attn_kh_kernel, two waves per
-// SIMD, for blocks of >= 16 key tiles; attn2 below that), 0 = attn2 always, 1 = attn_kh_kernel always
+// launch_attention's argument checks (the host emulation applies the same ones)
+inline void attn_check_args(const AttnArgs& a) {
+    ACEMI_CHECK(a.Hkv > 0 && a.Hq % a.Hkv == 0, "attention: Hq must be a multiple of Hkv");
+    const int rep = a.Hq / a.Hkv;
+    ACEMI_CHECK(rep == 1 || rep == 2 || rep == 4, "attention: n_rep must be 1, 2 or 4");
+    ACEMI_CHECK(a.nk_pad % ATTN_KT == 0 && a.nk_pad >= a.nk, "attention: nk_pad");
+    const int qpb = 128 / rep;
+    const int n_qt = (a.nq + qpb - 1) / qpb;
+    ACEMI_CHECK(a.nq_pad >= n_qt * qpb, "attention: nq_pad too small");
+    ACEMI_CHECK(!a.f8 || a.pv_split, "attention: the fp8 correction modes need pv_split");
+    if (a.split) {
+        ACEMI_CHECK(a.q_plane > 0 && a.k_plane > 0, "attention: split mode needs lo planes");
+        ACEMI_CHECK(!a.pv_split || a.v_plane > 0, "attention: hi/lo P.V needs the V lo plane");
+    } else if (a.pv_split) {
+        ACEMI_CHECK(a.f8 && a.v_plane > 0, "attention: pv8 mode needs the fp8 V lo plane");
+    }
+}
+inline AttnShape attn_shape_of(const AttnArgs& a) {
+    return {a.B,     a.Hq,       a.Hkv, a.nq,  a.nk, a.window, a.causal, a.part != nullptr,
+            a.split, a.pv_split, a.f8,  a.out_f32 != nullptr};
+}
+// The tests' override of this process's attention policy (attn_plan.h): every field that is not -1 replaces what the
+// environment / the device says; ATTN_POLICY_UNSET clears it.
+inline AttnPolicy& attn_policy_override() {
+    static AttnPolicy over = ATTN_POLICY_UNSET;
+    return over;
+}
+// Which kernel runs the f8c mode (the override's kh field alone): -1 = ACE_MI_ATTN_KH (0 never, 1 always) / default
+// (attn_kh_kernel, two waves per SIMD, for blocks of >= 16 key tiles; attn2 below that), 0 = attn2 always,
+// 1 = attn_kh_kernel always
 void attn_kh_mode(int mode);
 // Operand precision of the attention MFMAs: FP16 = single fp16 operands (two workgroups per CU),
 // SPLIT = hi/lo fp16 Q.K (three MFMAs per product) with fp16 P.V, F32 = hi/lo fp16 for both products

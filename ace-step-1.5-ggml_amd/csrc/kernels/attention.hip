@@ -48,6 +48,7 @@
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
+#include <type_traits>
 
 #include "../kernels.h"
 #include "lds_asm.h"
@@ -59,8 +60,8 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((address_space(3))) void lds_void;
 
-constexpr int D = 128;
-constexpr int KT = 64;                    // keys per tile
+constexpr int D = ATTN_D;
+constexpr int KT = ATTN_KT;               // keys per tile
 constexpr int K_BYTES = KT * D * 2;       // 16 KiB
 constexpr int V_BYTES = D * KT * 2;       // 16 KiB
 constexpr float PSCALE_LOG2 = 12.0f;
@@ -122,38 +123,6 @@ constexpr int RA = ACEMI_ATTN_RA;
 #endif
 constexpr int kAttnAblate = ACEMI_ATTN_ABLATE;
 
-// The workgroup's logical block (item, kv head, query tile) and key-range part.  Uniform layout: every block in
-// a.ksplit parts, XCD-aware order over all of them (the hardware deals launch index j to XCD j % 8; logical
-// index (j % 8) * per + j / 8 gives each XCD one contiguous run, i.e. the blocks of one (item, kv head), whose
-// K / V^T tiles they all stream, share one XCD's L2).  Tail split (a.split_from = F > 0, a multiple of 8): launch
-// indices [0, F) are whole blocks 0..F-1 (one full round), the rest the two key-range halves of blocks F..n-1
-// (the last, partial round split so it fills the chip), XCD-aware within each range.  Returns false for the up
-// to 7 empty trailing workgroups of a range.
-__device__ __forceinline__ bool attn_block(const AttnArgs& a, int n_blk, int& blk, int& part, int& parts) {
-    const int x = blockIdx.x;
-    auto xcd = [&](int i, int n) { return a.xcd_order ? (i & 7) * ((n + 7) >> 3) + (i >> 3) : i; };
-    if (a.split_from > 0) {
-        const int F = a.split_from;
-        if (x < F) {
-            blk = xcd(x, F);
-            part = 0;
-            parts = 1;
-            return blk < F;
-        }
-        const int n2 = 2 * (n_blk - F);
-        const int y = xcd(x - F, n2);
-        blk = F + (y >> 1);
-        part = y & 1;
-        parts = 2;
-        return y < n2;
-    }
-    const int n = n_blk * a.ksplit;
-    const int y = xcd(x, n);
-    blk = y / a.ksplit;
-    part = y % a.ksplit;
-    parts = a.ksplit;
-    return y < n;
-}
 static_assert(RA >= 1 && 2 * RA <= 15, "lgkmcnt counts at most 15 outstanding reads");
 // LDS reads issued after step p's own, i.e. those of steps p+1 .. p+RA (< n), for the counted lgkmcnt of step p
 template <class F>
@@ -245,8 +214,11 @@ __global__ void __launch_bounds__(256, OCC) attn2_kernel(AttnArgs a) {
     const int rep = a.Hq / a.Hkv;
     const int qpb = 128 / rep;
     const int n_qt = (a.nq + qpb - 1) / qpb;
-    int bid, split, ks;  // logical block, its key-range part (AttnArgs::part) and the block's number of parts
-    if (!attn_block(a, a.B * a.Hkv * n_qt, bid, split, ks)) return;
+    const AttnBlock ab = attn_block_of(a.ksplit, a.split_from, a.xcd_order, a.B * a.Hkv * n_qt, blockIdx.x);
+    if (!ab.valid) return;
+    // logical block, its key-range part (AttnArgs::part) and the block's number of parts
+    int bid = ab.blk;
+    const int split = ab.part, ks = ab.parts;
     const int qt = bid % n_qt;
     bid /= n_qt;
     const int kvh = bid % a.Hkv;
@@ -257,6 +229,9 @@ __global__ void __launch_bounds__(256, OCC) attn2_kernel(AttnArgs a) {
     const int qw0 = q0 + (wid % waves_per_head) * 32;
     const int qrow = qw0 + lq;
 
+    // attn_key_tiles (attn_plan.h), restated: calling it here gave another scalar prologue (one s_add fewer, other
+    // registers) and launch times outside the previous build's spread on the MI355X, so the kernels
+    // keep their own lines
     int klo = 0, khi = a.nk;
     if (a.window > 0) {
         klo = max(0, q0 - a.window);
@@ -820,8 +795,10 @@ __global__ void __launch_bounds__(512) attn_kh_kernel(AttnArgs a) {
     const int rep = a.Hq / a.Hkv;
     const int qpb = 128 / rep;
     const int n_qt = (a.nq + qpb - 1) / qpb;
-    int bid, split, ks;
-    if (!attn_block(a, a.B * a.Hkv * n_qt, bid, split, ks)) return;
+    const AttnBlock ab = attn_block_of(a.ksplit, a.split_from, a.xcd_order, a.B * a.Hkv * n_qt, blockIdx.x);
+    if (!ab.valid) return;
+    int bid = ab.blk;
+    const int split = ab.part, ks = ab.parts;
     const int qt = bid % n_qt;
     bid /= n_qt;
     const int kvh = bid % a.Hkv;
@@ -831,6 +808,7 @@ __global__ void __launch_bounds__(512) attn_kh_kernel(AttnArgs a) {
     const int q0 = qt * qpb;
     const int qrow = q0 + (wq % waves_per_head) * 32 + lq;
 
+    // attn_key_tiles (attn_plan.h), restated as in attn2_kernel
     int klo = 0, khi = a.nk;
     if (a.window > 0) {
         klo = max(0, q0 - a.window);
@@ -1431,199 +1409,99 @@ __global__ void __launch_bounds__(256) attn_merge_kernel(AttnArgs a) {
                    (uint32_t)to_act<F16OUT>(v[2] * inv) | ((uint32_t)to_act<F16OUT>(v[3] * inv) << 16));
 }
 
-int g_kh_mode = -1;
-
-template <bool F16OUT, bool SPLIT, bool PVS>
-void launch_t(const AttnArgs& a, dim3 grid, hipStream_t s, bool kh) {
-    const size_t lds = Ring<SPLIT, PVS>::BYTES;
+template <bool F16OUT, bool KBIAS>
+void launch_main(const AttnArgs& a, const AttnPlan& plan, hipStream_t s) {
+    const dim3 grid(plan.grid);
     // One workgroup per CU in every mode (round 6): each instance then runs one wave per SIMD, the only occupancy at
     // which attn2's hand-laid stream may reuse an MFMA's A / B register right after issuing it (tools/audit_mfma_war.py
     // classifies those pairs as single-wave).  Round 3's kernel (attn_kernel, ACE_MI_ATTN_V1) and the
     // two-per-CU fp16 instance are gone: the fp16 mode is a diagnostic precision, not a product one.
-    if constexpr (PVS) {
-        if constexpr (SPLIT) {
-            if (a.f8 && kh) {  // f8c at two waves per SIMD (launch_attention's policy)
-                if (a.kbias)
-                    hipLaunchKernelGGL((attn_kh_kernel<F16OUT, true>), grid, dim3(512), lds, s, a);
-                else
-                    hipLaunchKernelGGL((attn_kh_kernel<F16OUT, false>), grid, dim3(512), lds, s, a);
-                return;
-            }
-        }
-        if (a.f8) {  // f8c (SPLIT) or pv8 (fp16 Q.K)
-            if (a.kbias)
-                hipLaunchKernelGGL((attn2_kernel<F16OUT, SPLIT, true, true, 1, true>), grid, dim3(256), lds, s, a);
-            else
-                hipLaunchKernelGGL((attn2_kernel<F16OUT, SPLIT, true, false, 1, true>), grid, dim3(256), lds, s, a);
-            return;
-        }
+    if (plan.kernel == AttnKernel::AttnKh) {  // f8c at two waves per SIMD (attn_plan's rule)
+        hipLaunchKernelGGL((attn_kh_kernel<F16OUT, KBIAS>), grid, dim3(512), (Ring<true, true>::BYTES), s, a);
+        return;
     }
-    if constexpr (!SPLIT && PVS) {
-        throw std::runtime_error("attention: hi/lo P.V with fp16 Q.K exists only with fp8 corrections (pv8)");
+    auto attn2 = [&](auto split, auto pvs, auto f8) {
+        constexpr bool SPLIT = decltype(split)::value, PVS = decltype(pvs)::value, F8 = decltype(f8)::value;
+        hipLaunchKernelGGL((attn2_kernel<F16OUT, SPLIT, PVS, KBIAS, 1, F8>), grid, dim3(256), (Ring<SPLIT, PVS>::BYTES), s,
+                           a);
+    };
+    const std::true_type T{};
+    const std::false_type F{};
+    if (a.f8) {  // f8c (hi/lo Q.K) or pv8 (fp16 Q.K)
+        a.split ? attn2(T, T, T) : attn2(F, T, T);
+    } else if (a.pv_split) {
+        ACEMI_CHECK(a.split, "attention: hi/lo P.V with fp16 Q.K exists only with fp8 corrections (pv8)");
+        attn2(T, T, F);
     } else {
-        if (a.kbias)
-            hipLaunchKernelGGL((attn2_kernel<F16OUT, SPLIT, PVS, true, 1>), grid, dim3(256), lds, s, a);
-        else
-            hipLaunchKernelGGL((attn2_kernel<F16OUT, SPLIT, PVS, false, 1>), grid, dim3(256), lds, s, a);
+        a.split ? attn2(T, F, F) : attn2(F, F, F);
     }
+}
+
+template <bool F16OUT, bool OUTF32>
+void launch_merge(const AttnArgs& a, const AttnPlan& plan, hipStream_t s) {
+    const dim3 grid(plan.merge_grid);
+    switch (plan.merge) {
+        case AttnMerge::None: return;
+        case AttnMerge::Uniform2:
+            hipLaunchKernelGGL((attn_merge_kernel<F16OUT, 2, false, OUTF32>), grid, dim3(256), 0, s, a);
+            return;
+        case AttnMerge::Uniform4:
+            hipLaunchKernelGGL((attn_merge_kernel<F16OUT, 4, false, OUTF32>), grid, dim3(256), 0, s, a);
+            return;
+        case AttnMerge::Tail:
+            hipLaunchKernelGGL((attn_merge_kernel<F16OUT, 2, true, OUTF32>), grid, dim3(256), 0, s, a);
+            return;
+    }
+}
+
+// What the environment and the device say, read once per process, under the tests' override.  Unrecognised values
+// mean the default.
+AttnPolicy policy() {
+    static const AttnPolicy env = [] {
+        AttnPolicy p{};
+        const char* e = std::getenv("ACE_MI_ATTN_KSPLIT");
+        p.ksplit_mode = (e && (e[0] == '1' || e[0] == '2' || e[0] == '3' || e[0] == '4')) ? e[0] - '0' : 0;
+        e = std::getenv("ACE_MI_ATTN_TAIL_SPLIT");
+        p.tail = (e && e[0] == '0') ? 0 : 1;
+        e = std::getenv("ACE_MI_ATTN_TAIL_MIN");
+        p.tail_min = e ? std::max(2, std::atoi(e)) : 16;
+        e = std::getenv("ACE_MI_ATTN_XCD_ORDER");
+        p.xcd_order = (e && e[0] == '0') ? 0 : 1;
+        e = std::getenv("ACE_MI_ATTN_KH");
+        p.kh = (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1;
+        int dev = 0;
+        ACEMI_HIP(hipGetDevice(&dev));
+        ACEMI_HIP(hipDeviceGetAttribute(&p.n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+        return p;
+    }();
+    return attn_policy_with(env, attn_policy_override());
 }
 
 }  // namespace
 
 void launch_attention(ActType out_t, const AttnArgs& a, hipStream_t s) {
-    ACEMI_CHECK(a.Hkv > 0 && a.Hq % a.Hkv == 0, "attention: Hq must be a multiple of Hkv");
-    const int rep = a.Hq / a.Hkv;
-    ACEMI_CHECK(rep == 1 || rep == 2 || rep == 4, "attention: n_rep must be 1, 2 or 4");
-    ACEMI_CHECK(a.nk_pad % KT == 0 && a.nk_pad >= a.nk, "attention: nk_pad");
-    const int qpb = 128 / rep;
-    const int n_qt = (a.nq + qpb - 1) / qpb;
-    ACEMI_CHECK(a.nq_pad >= n_qt * qpb, "attention: nq_pad too small");
+    attn_check_args(a);
+    const AttnPlan plan = attn_plan(attn_shape_of(a), policy());
+    ACEMI_CHECK(plan.ksplit == 1 || plan.ksplit == 2 || plan.ksplit == 4,
+                "attention: the merge handles 2 or 4 key-split parts");
     AttnArgs b = a;
-    b.ksplit = 1;
-    b.split_from = 0;
-    {
-        static int xcd = -1;  // ACE_MI_ATTN_XCD_ORDER=0: plain block order (A/B measurements)
-        if (xcd < 0) {
-            const char* e = std::getenv("ACE_MI_ATTN_XCD_ORDER");
-            xcd = (e && e[0] == '0') ? 0 : 1;
-        }
-        b.xcd_order = xcd;
-    }
-    {
-        // a grid of fewer than ~1.6 rounds over the CUs idles a third of the chip in its last
-        // round: split each block's key range in two (B = 1 at 240 s: 376 blocks -> 752)
-        static int n_cu = 0;
-        if (n_cu == 0) {
-            int dev = 0;
-            ACEMI_HIP(hipGetDevice(&dev));
-            ACEMI_HIP(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-        }
-        const int64_t blocks = (int64_t)a.B * a.Hkv * n_qt;
-        const int span = a.window > 0 ? std::min(a.nk, qpb + 2 * a.window) : a.nk;
-        // (measured: full 240 s 317 -> 262 us incl. the merge; at 8 key tiles or fewer -- cross attention,
-        // sliding windows -- the extra prologue and merge cost more than the round saves)
-        // ACE_MI_ATTN_KSPLIT=1 never / 2 always (where a workspace exists) / 3 auto without the short-range split /
-        // 4 see below / auto
-        static int mode = -1;
-        if (mode < 0) {
-            const char* e = std::getenv("ACE_MI_ATTN_KSPLIT");
-            mode = (e && (e[0] == '1' || e[0] == '2' || e[0] == '3' || e[0] == '4')) ? e[0] - '0' : 0;
-        }
-        // blocks resident per CU: one in every mode (launch_t)
-        const int per_cu = 1;
-        const int64_t slots = (int64_t)n_cu * per_cu;
-        const int ntiles = (span + KT - 1) / KT;
-        int S = 1;
-        // tail split (default; ACE_MI_ATTN_TAIL_SPLIT=0: every block split): when the whole blocks overfill one
-        // round by at most half a round, run one round of whole blocks and split only the rest -- the same
-        // 1 + 1/2 rounds of key tiles per CU as splitting every block, one block prologue fewer per CU, a third of
-        // the rows through the merge (240 s, B = 1: 256 whole blocks + 2 x 120 halves).  ACE_MI_ATTN_TAIL_MIN: the
-        // fewest key tiles per block for which it is used where every-block splitting is not (default 16 = never)
-        static int tail = -1, tail_min = 0;
-        if (tail < 0) {
-            const char* e = std::getenv("ACE_MI_ATTN_TAIL_SPLIT");
-            tail = (e && e[0] == '0') ? 0 : 1;
-            const char* m = std::getenv("ACE_MI_ATTN_TAIL_MIN");
-            tail_min = m ? std::max(2, std::atoi(m)) : 16;
-        }
-        const int64_t F = slots & ~int64_t(7);
-        const bool tail_fits = tail && (mode == 0 || mode == 3) && F > 0 && blocks > F && 2 * (blocks - F) <= slots;
-        if (ntiles >= 16) {
-            if (blocks * 10 < slots * 16) S = 2;
-        } else if (mode == 4 || (mode == 0 && blocks * 2 <= slots)) {
-            // short key ranges (cross attention, sliding windows, short sequences) split too when the grid fills at
-            // most half a round (ACE_MI_ATTN_KSPLIT=4: whatever the grid), while it stays within one round and every
-            // part keeps >= 2 key tiles.  Round 3 (the first kernel, profiles/r03_trace_60s_*.txt) lost: 698 us +
-            // 48 merges 275 us per forward against ~950 us unsplit.  With attn2 it pays: 60 s (96 blocks on 256 CUs)
-            // 165.1 against 163.1-163.4 steps/s (profiles/r05/attn_ksplit_short.txt)
-            while (S < 4 && blocks * 2 * S <= slots && ntiles >= 4 * S) S *= 2;
-        } else if (tail_fits && ntiles >= tail_min) {
-            S = 2;
-        }
-        if (a.part && mode == 2) b.ksplit = 2;
-        else if (a.part && (mode == 0 || mode == 3 || mode == 4)) b.ksplit = S;
-        if (tail_fits && b.ksplit == 2) b.split_from = (int)F;
-        // (round 5 also built an in-kernel merge -- the last part of a group merging through an sc1 partial round
-        // trip and a ticket, no merge launch: neutral at 60 s, 4 % slower lines at 240 s, profiles/r05/attn_fused_merge.txt;
-        // removed from the product library in round 6)
-    }
-    // (f32 output, AttnArgs::out_f32: the same split policy -- whole blocks write f32 rows themselves, the merges
-    // below write f32 rows; until round 6 every block ran in two key-range parts with a full merge, 0.84 ms per 240 s
-    // step of the quantized-activation mode)
-    const int64_t n_blk = (int64_t)a.B * a.Hkv * n_qt;
-    // XCD-aware order (attn_block): whole multiples of 8 launch indices per range
-    const dim3 grid(b.split_from > 0 ? (unsigned)(b.split_from + 8 * ((2 * (n_blk - b.split_from) + 7) / 8))
-                                     : (unsigned)(8 * ((n_blk * b.ksplit + 7) / 8)));
+    b.ksplit = plan.ksplit;
+    b.split_from = plan.split_from;
+    b.xcd_order = plan.xcd_order;
     const bool f16 = out_t == ActType::F16;
-    ACEMI_CHECK(!a.f8 || a.pv_split, "attention: the fp8 correction modes need pv_split");
-    // f8c kernel: attn_kh_kernel (two waves per SIMD) where a block streams >= 16 key tiles (full self-attention
-    // layers; measured 240 s: full 173.3 vs 175.2 us, bs 8 1.340 vs 1.355 ms), attn2 on short ranges (cross 50.8 vs
-    // 48.1 us, sliding 42.4 vs 41.4: the 8-wave prologue and the pair merge outweigh the gain), profiles/r06/attn_kh/
-    bool kh;
-    {
-        static int env = -2;
-        if (env == -2) {
-            const char* e = std::getenv("ACE_MI_ATTN_KH");
-            env = (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1;
-        }
-        const int mode = g_kh_mode >= 0 ? g_kh_mode : env;
-        const int span = a.window > 0 ? std::min(a.nk, qpb + 2 * a.window) : a.nk;
-        kh = mode == 1 || (mode < 0 && (span + KT - 1) / KT >= 16);
-    }
-    if (a.split) {
-        ACEMI_CHECK(a.q_plane > 0 && a.k_plane > 0, "attention: split mode needs lo planes");
-        if (a.pv_split) {
-            ACEMI_CHECK(a.v_plane > 0, "attention: hi/lo P.V needs the V lo plane");
-            f16 ? launch_t<true, true, true>(b, grid, s, kh) : launch_t<false, true, true>(b, grid, s, kh);
-        } else {
-            f16 ? launch_t<true, true, false>(b, grid, s, kh) : launch_t<false, true, false>(b, grid, s, kh);
-        }
-    } else if (a.pv_split) {
-        ACEMI_CHECK(a.f8 && a.v_plane > 0, "attention: pv8 mode needs the fp8 V lo plane");
-        f16 ? launch_t<true, false, true>(b, grid, s, kh) : launch_t<false, false, true>(b, grid, s, kh);
-    } else {
-        f16 ? launch_t<true, false, false>(b, grid, s, kh) : launch_t<false, false, false>(b, grid, s, kh);
-    }
+    if (f16)
+        a.kbias ? launch_main<true, true>(b, plan, s) : launch_main<true, false>(b, plan, s);
+    else
+        a.kbias ? launch_main<false, true>(b, plan, s) : launch_main<false, false>(b, plan, s);
     ACEMI_HIP(hipGetLastError());
-    if (b.ksplit > 1) {
-        const int64_t rows = (int64_t)a.B * a.nq * a.Hq;
-        ACEMI_CHECK(b.ksplit == 2 || b.ksplit == 4, "attention: the merge handles 2 or 4 key-split parts");
-        const dim3 mgrid((unsigned)((rows + 7) / 8));
-        if (a.out_f32) {
-            if (b.split_from > 0)
-                hipLaunchKernelGGL((attn_merge_kernel<false, 2, true, true>), dim3((unsigned)((n_blk - b.split_from) * 16)),
-                                   dim3(256), 0, s, b);
-            else if (b.ksplit == 2)
-                hipLaunchKernelGGL((attn_merge_kernel<false, 2, false, true>), mgrid, dim3(256), 0, s, b);
-            else
-                hipLaunchKernelGGL((attn_merge_kernel<false, 4, false, true>), mgrid, dim3(256), 0, s, b);
-        } else if (b.split_from > 0) {
-            const dim3 tgrid((unsigned)((n_blk - b.split_from) * 16));  // 128 rows per split block, 8 per workgroup
-            if (out_t == ActType::F16)
-                hipLaunchKernelGGL((attn_merge_kernel<true, 2, true>), tgrid, dim3(256), 0, s, b);
-            else
-                hipLaunchKernelGGL((attn_merge_kernel<false, 2, true>), tgrid, dim3(256), 0, s, b);
-        } else if (b.ksplit == 2) {
-            if (out_t == ActType::F16)
-                hipLaunchKernelGGL((attn_merge_kernel<true, 2>), mgrid, dim3(256), 0, s, b);
-            else
-                hipLaunchKernelGGL((attn_merge_kernel<false, 2>), mgrid, dim3(256), 0, s, b);
-        } else {
-            if (out_t == ActType::F16)
-                hipLaunchKernelGGL((attn_merge_kernel<true, 4>), mgrid, dim3(256), 0, s, b);
-            else
-                hipLaunchKernelGGL((attn_merge_kernel<false, 4>), mgrid, dim3(256), 0, s, b);
-        }
-        ACEMI_HIP(hipGetLastError());
-    }
+    if (plan.merge == AttnMerge::None) return;
+    if (a.out_f32)
+        launch_merge<false, true>(b, plan, s);
+    else
+        f16 ? launch_merge<true, false>(b, plan, s) : launch_merge<false, false>(b, plan, s);
+    ACEMI_HIP(hipGetLastError());
 }
 
-void attn_kh_mode(int mode) { g_kh_mode = mode; }
-
-size_t attn_part_floats(int B, int nq, int Hq) {
-    const size_t rows = (size_t)B * nq * Hq;
-    // up to four key-split parts: unnormalised O rows + (running max, sum) per row
-    return 4 * rows * (D + 2);
-}
+void attn_kh_mode(int mode) { attn_policy_override() = {-1, -1, -1, -1, mode, -1}; }
 
 }  // namespace acemi

@@ -131,7 +131,7 @@ void DitEngine::prepare_shape(int B, int Np, int L) {
     ensure(kh_, (size_t)2 * B * c.hkv * Npad * D * 2);
     ensure(vt_, (size_t)2 * B * c.hkv * D * Npad * 2);
     ensure(kbias_, (size_t)B * Npad * 4);
-    ensure(attn_part_, attn_part_floats(B, (int)Np, c.hq) * 4);
+    ensure(attn_part_, attn_part_floats((size_t)B * Np * c.hq) * 4);
     if (L > 0) {
         const int64_t Lpad = round_up(L, 64);
         const int64_t Me = (int64_t)B * L;

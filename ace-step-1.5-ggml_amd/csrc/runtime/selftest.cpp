@@ -90,11 +90,11 @@ struct AttnSetup {
         : dq((size_t)B * nq * Hq * 128 * 4), dkv((size_t)B * nk * 2 * Hkv * 128 * 4), dm((size_t)B * nk * 4),
           dqh((size_t)2 * B * Hq * acemi::round_up(nq, 128) * 128 * 2), dkh((size_t)2 * B * Hkv * acemi::round_up(nk, 128) * 128 * 2),
           dvt((size_t)2 * B * Hkv * 128 * acemi::round_up(nk, 128) * 2), dkb((size_t)B * acemi::round_up(nk, 128) * 4),
-          dout((size_t)B * nq * Hq * 128 * 2), dpart(acemi::attn_part_floats(B, nq, Hq) * 4) {
+          dout((size_t)B * nq * Hq * 128 * 2), dpart(acemi::attn_part_floats((size_t)B * nq * Hq) * 4) {
         using namespace acemi;
         const int D = 128;
         const int nq_pad = (int)round_up(nq, 128), nk_pad = (int)round_up(nk, 128);
-        ACEMI_HIP(hipMemset(dpart.p, 0, attn_part_floats(B, nq, Hq) * 4));  // the key-split tickets start at 0
+        ACEMI_HIP(hipMemset(dpart.p, 0, attn_part_floats((size_t)B * nq * Hq) * 4));  // the key-split tickets start at 0
         nqf = (size_t)B * nq * Hq * D;
         const size_t nkvf = (size_t)B * nk * 2 * Hkv * D;
         ACEMI_HIP(hipMemcpy(dq.p, q, nqf * 4, hipMemcpyHostToDevice));
@@ -762,6 +762,60 @@ ace_ggml_status ace_mi_kernel_gemm_a8_mode(int32_t mode) {
 ace_ggml_status ace_mi_kernel_attn_kh(int32_t mode) {
     if (mode < -1 || mode > 1) return ACE_GGML_ERR_INVALID_ARG;
     acemi::attn_kh_mode(mode);
+    return ACE_GGML_OK;
+}
+
+// {ksplit_mode, tail, tail_min, xcd_order, kh, n_cu}, each -1 (unset) or inside its range
+static bool attn_policy_fields_ok(const int32_t f[6], bool allow_unset) {
+    const int32_t lo[6] = {0, 0, 2, 0, 0, 1}, hi[6] = {4, 1, 1 << 20, 1, 1, 1 << 20};
+    for (int i = 0; i < 6; ++i) {
+        const bool unset = f[i] == -1 && (allow_unset || i == 4);  // (kh = -1: the rule, also in a full policy)
+        if (!unset && (f[i] < lo[i] || f[i] > hi[i])) return false;
+    }
+    return true;
+}
+static acemi::AttnPolicy attn_policy_of(const int32_t f[6]) { return {f[0], f[1], f[2], f[3], f[4], f[5]}; }
+
+// The whole attention policy of this process (csrc/attn_plan.h): a field of -1 leaves the environment / the device in
+// charge; all six -1 clears the override.
+ace_ggml_status ace_mi_kernel_attn_policy(const int32_t fields[6]) {
+    if (!fields || !attn_policy_fields_ok(fields, true)) return ACE_GGML_ERR_INVALID_ARG;
+    acemi::attn_policy_override() = attn_policy_of(fields);
+    return ACE_GGML_OK;
+}
+
+// The attention launch plan (csrc/attn_plan.h) for the CPU tests: pure, no device.
+ace_ggml_status ace_mi_attn_plan(const int32_t shape[12], const int32_t policy[6], int32_t plan[8]) {
+    using namespace acemi;
+    if (!shape || !policy || !plan || !attn_policy_fields_ok(policy, false)) return ACE_GGML_ERR_INVALID_ARG;
+    const AttnShape a{shape[0],      shape[1],      shape[2],      shape[3],      shape[4],       shape[5],
+                      shape[6] != 0, shape[7] != 0, shape[8] != 0, shape[9] != 0, shape[10] != 0, shape[11] != 0};
+    if (a.B < 1 || a.Hkv < 1 || a.Hq % a.Hkv != 0 || a.nq < 1 || a.nk < 1 || a.window < 0) return ACE_GGML_ERR_INVALID_ARG;
+    const int rep = a.Hq / a.Hkv;
+    if (rep != 1 && rep != 2 && rep != 4) return ACE_GGML_ERR_INVALID_ARG;
+    const AttnPlan p = attn_plan(a, attn_policy_of(policy));
+    const int32_t out[8] = {p.ksplit,        p.split_from,      p.xcd_order,      p.n_blk,
+                            (int32_t)p.grid, (int32_t)p.kernel, (int32_t)p.merge, (int32_t)p.merge_grid};
+    std::copy(out, out + 8, plan);
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_attn_plan_block(int32_t ksplit, int32_t split_from, int32_t xcd_order, int32_t n_blk, int32_t x,
+                                       int32_t out[4]) {
+    if (!out || ksplit < 1 || split_from < 0 || split_from > n_blk || n_blk < 1 || x < 0) return ACE_GGML_ERR_INVALID_ARG;
+    const acemi::AttnBlock b = acemi::attn_block_of(ksplit, split_from, xcd_order, n_blk, x);
+    const int32_t f[4] = {b.blk, b.part, b.parts, b.valid};
+    std::copy(f, f + 4, out);
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_attn_plan_tiles(int32_t nk, int32_t window, int32_t causal, int32_t q0, int32_t qpb, int32_t part,
+                                       int32_t parts, int32_t out[2]) {
+    if (!out || nk < 1 || window < 0 || q0 < 0 || qpb < 1 || parts < 1 || part < 0 || part >= parts)
+        return ACE_GGML_ERR_INVALID_ARG;
+    const acemi::AttnKeyTiles t = acemi::attn_key_tiles(nk, window, causal != 0, q0, qpb, part, parts);
+    out[0] = t.kt_begin;
+    out[1] = t.n;
     return ACE_GGML_OK;
 }
 

@@ -95,6 +95,25 @@ ACE_GGML_API ace_ggml_status ace_mi_kernel_gemm_a8_mode(int32_t mode);
  * (the two-waves-per-SIMD kernel for blocks of >= 16 key tiles), 0 = the one-wave-per-SIMD kernel, 1 = the two-wave
  * kernel everywhere.  Same results within the f8c bound. */
 ACE_GGML_API ace_ggml_status ace_mi_kernel_attn_kh(int32_t mode);
+/* The whole attention launch policy of this process (csrc/attn_plan.h; ace_mi_kernel_attn_kh is its kh field alone):
+ * fields = {ksplit_mode 0 auto / 1..4 as ACE_MI_ATTN_KSPLIT, tail 0 / 1, tail_min >= 2, xcd_order 0 / 1, kh 0 / 1,
+ * n_cu >= 1 (the CU count the split rules plan for: a small one makes a small shape behave like an over-full chip)};
+ * a field of -1 leaves the environment / the device in charge, six times -1 clears the override. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_attn_policy(const int32_t fields[6]);
+/* The attention launch plan (csrc/attn_plan.h), without a device.
+ * ace_mi_attn_plan: shape = {B, Hq, Hkv, nq, nk, window, causal, a key-split workspace exists, split, pv_split, f8,
+ * f32 output}, policy = the six fields above, all set (kh may be -1: the rule) -> plan = {ksplit, split_from, xcd_order,
+ * logical blocks, main grid, kernel (0 attn2_kernel, 1 attn_kh_kernel), merge (0 none, 1 two parts, 2 four parts,
+ * 3 tail), merge grid}.
+ * ace_mi_attn_plan_block: launch index x of a plan -> out = {logical block, key-range part, the block's number of
+ * parts, valid (0: an empty trailing workgroup)}.
+ * ace_mi_attn_plan_tiles: the key tiles out = {first, count} that part `part` of `parts` streams for the queries
+ * [q0, q0 + qpb). */
+ACE_GGML_API ace_ggml_status ace_mi_attn_plan(const int32_t shape[12], const int32_t policy[6], int32_t plan[8]);
+ACE_GGML_API ace_ggml_status ace_mi_attn_plan_block(int32_t ksplit, int32_t split_from, int32_t xcd_order,
+                                                    int32_t n_blk, int32_t x, int32_t out[4]);
+ACE_GGML_API ace_ggml_status ace_mi_attn_plan_tiles(int32_t nk, int32_t window, int32_t causal, int32_t q0,
+                                                    int32_t qpb, int32_t part, int32_t parts, int32_t out[2]);
 /* LoRA merge kernel (launch_lora_merge, csrc/kernels.h): n_jobs jobs in ONE launch on one matrix pair.  base
  * [total_rows][ld_base] (NULL = in place on out) and out [total_rows][ld_out] are raw 16-bit words of fmt (0 bf16,
  * 1 fp16); out holds its initial content on entry and the merged image on return, so a caller sees which words were

@@ -231,10 +231,14 @@ void touch(const T* p, int64_t n) {
 }
 
 void attn_kh_mode(int) {}
-size_t attn_part_floats(int B, int nq, int Hq) { return 2 * (size_t)B * nq * Hq * (128 + 2); }
 
 void launch_attention(ActType out_t, const AttnArgs& a, hipStream_t) {
+    attn_check_args(a);
+    // the real launcher's plan, for a 256-CU device unless the override says otherwise (the environment is not read)
+    const AttnPlan plan = attn_plan(attn_shape_of(a), attn_policy_with(attn_policy_default(256), attn_policy_override()));
     const int D = 128, rep = a.Hq / a.Hkv;
+    // the partials the split kernels and the merge go through: ksplit planes of O rows, then (max, sum) per row
+    if (plan.ksplit > 1) touch(a.part, (int64_t)plan.ksplit * a.B * a.nq * a.Hq * (D + 2));
     {  // attn_kernel footprint: Q rows up to nq_pad, K / V^T tiles up to nk_pad, both planes when split
         const int64_t nq = (int64_t)a.B * a.Hq * a.nq_pad * D, nk = (int64_t)a.B * a.Hkv * a.nk_pad * D;
         touch(a.q, a.split ? a.q_plane + nq : nq);
