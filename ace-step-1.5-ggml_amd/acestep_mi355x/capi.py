@@ -57,7 +57,8 @@ SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_ker
                     "ace_mi_kernel_lm_skinny", "ace_mi_kernel_lm_embed", "ace_mi_kernel_lm_qkv_post",
                     "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention", "ace_mi_kernel_lm_skinny_q",
                     "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_select",
-                    "ace_mi_kernel_conv_gemm", "ace_mi_kernel_conv_out", "ace_mi_kernel_pack_f16")
+                    "ace_mi_kernel_conv_gemm", "ace_mi_kernel_conv_out", "ace_mi_kernel_pack_f16",
+                    "ace_mi_rope_table", "ace_mi_rope_table_steps")
 
 # qtype codes of ace_mi_quantize & co. (names as parse_quant_type, acestep_dit_model.cpp:27-37)
 QTYPES = {"q8_0": 1, "q4_k": 2, "q6_k": 3,
@@ -300,6 +301,15 @@ def _bind_gemm_variants(lib: ctypes.CDLL) -> ctypes.CDLL:
     return lib
 
 
+def _bind_rope_table(lib: ctypes.CDLL) -> ctypes.CDLL:
+    i32, ip, fp = ctypes.c_int32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_float)
+    lib.ace_mi_rope_table.argtypes = [i32, i32, ctypes.c_float, fp, fp]
+    lib.ace_mi_rope_table.restype = ctypes.c_int
+    lib.ace_mi_rope_table_steps.argtypes = [i32, ip, ip, fp, ip, fp, fp]
+    lib.ace_mi_rope_table_steps.restype = ctypes.c_int
+    return lib
+
+
 def _bind_attn_plan(lib: ctypes.CDLL) -> ctypes.CDLL:
     i32, ip = ctypes.c_int32, ctypes.POINTER(ctypes.c_int32)
     lib.ace_mi_kernel_attn_policy.argtypes = [ip]
@@ -366,6 +376,7 @@ def load_selftest_library() -> ctypes.CDLL:
     _bind_attn_plan(lib)
     _bind_lm_kernels(lib)
     _bind_vae_kernels(lib)
+    _bind_rope_table(lib)
     _SELFTEST = lib
     return lib
 
@@ -1496,6 +1507,30 @@ def gemm_variant_row(vid: int, lib=None) -> Optional[dict]:
 def gemm_variant_arg_ok(variant: int, allow_unchecked: bool = False, lib=None) -> bool:
     lib = _bind_gemm_variants(lib) if lib is not None else load_selftest_library()
     return lib.ace_mi_gemm_variant_arg_ok(int(variant), int(allow_unchecked)) == ACE_GGML_OK
+
+
+def rope_table(n: int, head_dim: int, theta: float, lib=None):
+    """(cos, sin), each [n][head_dim / 2] float32: the RoPE table the engines build (csrc/runtime/devmem.h).  `lib`: a
+    loaded library that exports the entry, bound or not (default: the GPU self-test library)."""
+    lib = _bind_rope_table(lib) if lib is not None else load_selftest_library()
+    cs, sn = (np.empty((n, head_dim // 2), np.float32) for _ in range(2))
+    if lib.ace_mi_rope_table(int(n), int(head_dim), float(theta), _fptr(cs), _fptr(sn)) != ACE_GGML_OK:
+        raise ValueError((n, head_dim, theta))
+    return cs, sn
+
+
+def rope_table_steps(steps, lib=None):
+    """One table through ensure(n, head_dim, theta) for each triple of `steps`: (rows held after each call, cos, sin of
+    the final table, each [rows[-1]][head_dim / 2] float32)."""
+    lib = _bind_rope_table(lib) if lib is not None else load_selftest_library()
+    n = np.array([s[0] for s in steps], np.int32)
+    hd = np.array([s[1] for s in steps], np.int32)
+    th = np.array([s[2] for s in steps], np.float32)
+    rows = np.zeros(len(steps), np.int32)
+    cs, sn = (np.empty((int(n.max()), int(hd[-1]) // 2), np.float32) for _ in range(2))
+    if lib.ace_mi_rope_table_steps(len(steps), _iptr(n), _iptr(hd), _fptr(th), _iptr(rows), _fptr(cs), _fptr(sn)) != ACE_GGML_OK:
+        raise ValueError(steps)
+    return rows.tolist(), cs[:rows[-1]], sn[:rows[-1]]
 
 
 def kernel_attn_kh(mode: int) -> None:

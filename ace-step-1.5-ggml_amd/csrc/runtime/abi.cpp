@@ -54,10 +54,8 @@ void ace_ggml_destroy(ace_ggml_context* ctx) {
     ctx->vae.reset();
     ctx->text.reset();
     ctx->lm.reset();
-    if (ctx->d_vae) (void)hipFree(ctx->d_vae);
-    if (ctx->d_in) (void)hipFree(ctx->d_in);
-    if (ctx->d_v) (void)hipFree(ctx->d_v);
-    if (ctx->d_sched) (void)hipFree(ctx->d_sched);
+    // freed here, before the stream goes, as ever (one not listed is still freed by `delete ctx`, after the stream)
+    for (acemi::DevBuf* b : {&ctx->d_vae, &ctx->d_in, &ctx->d_v, &ctx->d_sched}) b->release();
     if (ctx->stream) {
         try {
             acemi::gemm_splitk_release(ctx->stream);
@@ -117,8 +115,8 @@ ace_ggml_status ace_ggml_dit_forward(ace_ggml_context* ctx, const float* hidden_
         const size_t o_h = 0, o_c = o_h + al(n_h * 4), o_e = o_c + al(n_c * 4), o_m = o_e + al(n_e * 4),
                      o_em = o_m + al((size_t)seq_len * 4), o_t = o_em + al((size_t)L * 4 + 4), o_out = o_t + 256,
                      total = o_out + al(n_h * 4);
-        ensure_dev(ctx->d_in, ctx->d_in_bytes, total);
-        char* base = static_cast<char*>(ctx->d_in);
+        ctx->d_in.ensure(total);
+        char* base = ctx->d_in.as<char>();
         acemi::ForwardIO io;
         io.B = 1;
         io.T = seq_len;
@@ -189,7 +187,7 @@ ace_ggml_status ace_mi_dit_get_info(ace_ggml_context* ctx, ace_mi_dit_info* out)
     out->sliding_window = c.sliding_window;
     out->act_type = static_cast<int32_t>(m.act);
     out->device = ctx->device;
-    out->weight_bytes = static_cast<int64_t>(m.weight_bytes);
+    out->weight_bytes = static_cast<int64_t>(m.arena.bytes());
     return ACE_GGML_OK;
 }
 
@@ -309,17 +307,15 @@ ace_ggml_status run_sampler(ace_ggml_context* ctx, int32_t batch, float* d_xt, c
         hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
         const auto& c = ctx->dit->model().cfg;
         const size_t n = (size_t)batch * seq_len * c.audio_dim;
-        void* vp = ctx->d_v;
-        ensure_dev(vp, ctx->d_v_bytes, n * 4);
-        ctx->d_v = static_cast<float*>(vp);
+        ctx->d_v.ensure(n * 4);
+        float* d_v = ctx->d_v.as<float>();
         std::vector<float> tt((size_t)n_steps * batch);
         for (int i = 0; i < n_steps; ++i)
             for (int b = 0; b < batch; ++b) tt[(size_t)i * batch + b] = schedule[i];
-        void* sp = ctx->d_sched;
         // sized generously so a longer loop later does not reallocate (hipFree syncs the device)
-        ensure_dev(sp, ctx->d_sched_bytes, std::max<size_t>(tt.size() * 4, 64 * 1024));
-        ctx->d_sched = static_cast<float*>(sp);
-        ACEMI_HIP(hipMemcpyAsync(ctx->d_sched, tt.data(), tt.size() * 4, hipMemcpyHostToDevice, s));
+        ctx->d_sched.ensure(std::max<size_t>(tt.size() * 4, 64 * 1024));
+        float* d_sched = ctx->d_sched.as<float>();
+        ACEMI_HIP(hipMemcpyAsync(d_sched, tt.data(), tt.size() * 4, hipMemcpyHostToDevice, s));
         ACEMI_HIP(hipStreamSynchronize(s));
         acemi::ForwardIO io;
         io.B = batch;
@@ -330,10 +326,10 @@ ace_ggml_status run_sampler(ace_ggml_context* ctx, int32_t batch, float* d_xt, c
         io.enc = d_enc;
         io.mask = d_mask;
         io.enc_mask = d_enc_mask;
-        io.out = ctx->d_v;
+        io.out = d_v;
         io.max_layers = max_layers_env();
         // every step's timestep is known now: the timestep MLPs of all steps in one pass (r = t in the sampler)
-        const auto ts = ctx->dit->precompute_timesteps(ctx->d_sched, ctx->d_sched, n_steps * batch, s);
+        const auto ts = ctx->dit->precompute_timesteps(d_sched, d_sched, n_steps * batch, s);
         const int H = c.hidden;
         bool switched = false;
         for (int i = 0; i < n_steps; ++i) {
@@ -349,18 +345,18 @@ ace_ggml_status run_sampler(ace_ggml_context* ctx, int32_t batch, float* d_xt, c
             }
             io.reuse_cross = cache_cross && !fresh;
             io.reuse_stage = i > 0;  // quantized weights: dequantized once per call (engine.h)
-            io.t = ctx->d_sched + (size_t)i * batch;
+            io.t = d_sched + (size_t)i * batch;
             io.r = io.t;
             io.ts_proj = ts.proj + (size_t)i * batch * 6 * H;
             io.ts_temb_t = ts.temb_t + (size_t)i * batch * H;
             io.ts_temb_r = ts.temb_r + (size_t)i * batch * H;
             ctx->dit->forward(io, s);
             if (i + 1 == n_steps) {  // final step: x0 = xt - v * t
-                acemi::launch_euler(d_xt, ctx->d_v, (int64_t)n, schedule[i], s);
+                acemi::launch_euler(d_xt, d_v, (int64_t)n, schedule[i], s);
             } else if (sde) {
-                acemi::launch_sde(d_xt, ctx->d_v, d_noise + (size_t)i * n, (int64_t)n, schedule[i], schedule[i + 1], s);
+                acemi::launch_sde(d_xt, d_v, d_noise + (size_t)i * n, (int64_t)n, schedule[i], schedule[i + 1], s);
             } else {
-                acemi::launch_euler(d_xt, ctx->d_v, (int64_t)n, schedule[i] - schedule[i + 1], s);
+                acemi::launch_euler(d_xt, d_v, (int64_t)n, schedule[i] - schedule[i + 1], s);
             }
         }
     } catch (const std::exception& e) {
@@ -576,8 +572,8 @@ ace_ggml_status ace_ggml_vae_decode(ace_ggml_context* ctx, const float* latents,
         if (out_size < needed) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "output buffer too small for actual output");
         const size_t n_in = (size_t)n_frames * c.decoder_input_channels * sizeof(float);
         const size_t o_out = (n_in + 255) & ~size_t(255);
-        ensure_dev(ctx->d_vae, ctx->d_vae_bytes, o_out + needed);
-        char* base = static_cast<char*>(ctx->d_vae);
+        ctx->d_vae.ensure(o_out + needed);
+        char* base = ctx->d_vae.as<char>();
         ACEMI_HIP(hipMemcpyAsync(base, latents, n_in, hipMemcpyHostToDevice, s));
         ACEMI_HIP(hipStreamSynchronize(s));
         const auto t1 = std::chrono::steady_clock::now();
@@ -620,8 +616,8 @@ ace_ggml_status ace_ggml_vae_encode(ace_ggml_context* ctx, const float* audio, i
         if (out_size < needed) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "output buffer too small for actual output");
         const size_t n_in = (size_t)n_samples * c.audio_channels * sizeof(float);
         const size_t o_out = (n_in + 255) & ~size_t(255);
-        ensure_dev(ctx->d_vae, ctx->d_vae_bytes, o_out + needed);
-        char* base = static_cast<char*>(ctx->d_vae);
+        ctx->d_vae.ensure(o_out + needed);
+        char* base = ctx->d_vae.as<char>();
         ACEMI_HIP(hipMemcpyAsync(base, audio, n_in, hipMemcpyHostToDevice, s));
         ctx->vae->encode(reinterpret_cast<const float*>(base), n_samples, reinterpret_cast<float*>(base + o_out), s);
         ACEMI_HIP(hipMemcpyAsync(out, base + o_out, needed, hipMemcpyDeviceToHost, s));

@@ -16,29 +16,6 @@ BlockRunner::BlockRunner() {
     pv_split_ = prec == AttnPrecision::F32;
 }
 
-BlockRunner::~BlockRunner() {
-    for (Buf* b : {&x_, &act_, &attn_, &act2_, &qkv_, &qh_, &kh_, &vt_, &kbias_, &cos_, &sin_})
-        if (b->p) (void)hipFree(b->p);
-}
-
-void BlockRunner::ensure(Buf& b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return;
-    if (b.p) {
-        ACEMI_HIP(hipDeviceSynchronize());
-        ACEMI_HIP(hipFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
-    }
-    const size_t alloc = (bytes + 255) & ~size_t(255);
-    ACEMI_HIP(hipMalloc(&b.p, alloc));
-    ACEMI_HIP(hipMemset(b.p, 0, alloc));
-    // hipMemset runs on the legacy null stream, which does not order against the library's
-    // non-blocking streams: finish it before any kernel can write the new buffer
-    ACEMI_HIP(hipDeviceSynchronize());
-    b.bytes = alloc;
-}
-
 float* BlockRunner::x(int64_t rows, int H) {
     ensure(x_, (size_t)rows * H * 4);
     return get<float>(x_);
@@ -64,27 +41,7 @@ void BlockRunner::run(const BlockShape& sh, const std::vector<DevLayer>& layers,
     ensure(kh_, (size_t)2 * k_plane * 2);
     ensure(vt_, (size_t)2 * k_plane * 2);
     ensure(kbias_, (size_t)B * Npad * 4);
-    if (rope_n_ != n || rope_theta_ != sh.rope_theta) {  // positions 0..n-1 of each item, ggml's recurrence
-        const int half = D / 2;
-        const float theta_scale = powf(sh.rope_theta, -2.0f / (float)D);
-        std::vector<float> cs((size_t)n * half), sn((size_t)n * half);
-        for (int p = 0; p < n; ++p) {
-            float theta = (float)p;
-            for (int i = 0; i < half; ++i) {
-                cs[(size_t)p * half + i] = (float)std::cos((double)theta);  // correctly rounded cosf / sinf
-                sn[(size_t)p * half + i] = (float)std::sin((double)theta);
-                theta *= theta_scale;
-            }
-        }
-        ACEMI_HIP(hipStreamSynchronize(s));  // the previous pass may still read the old table
-        ensure(cos_, cs.size() * 4);
-        ensure(sin_, sn.size() * 4);
-        ACEMI_HIP(hipMemcpy(cos_.p, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
-        ACEMI_HIP(hipMemcpy(sin_.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
-        ACEMI_HIP(hipDeviceSynchronize());  // null-stream copy: done before any stream reads it
-        rope_n_ = n;
-        rope_theta_ = sh.rope_theta;
-    }
+    rope_.ensure(n, D, sh.rope_theta, s);
     float* x = get<float>(x_);
     uint16_t* act = get<uint16_t>(act_);
     uint16_t* attn = get<uint16_t>(attn_);
@@ -98,8 +55,8 @@ void BlockRunner::run(const BlockShape& sh, const std::vector<DevLayer>& layers,
         launch_rmsnorm_mod(at, x, M, H, ly.self_norm, nullptr, nullptr, 0, n, sh.eps, act, s);
         launch_gemm(act, H, ly.w_qkv.view(), M, qd + 2 * kd, H, epi_store_f32(qkv, qd + 2 * kd), s);
         if (after_qkv) (*after_qkv)(li, qkv, qd + 2 * kd);
-        launch_attn_prep(self_prep(dims, planes, qkv, qd + 2 * kd, ly.sq_norm, ly.sk_norm, get<float>(cos_),
-                                   get<float>(sin_), qh, kh, vt),
+        launch_attn_prep(self_prep(dims, planes, qkv, qd + 2 * kd, ly.sq_norm, ly.sk_norm, rope_.cos(), rope_.sin(), qh,
+                                   kh, vt),
                          s);
         launch_attention(at,
                          attn_args(dims, planes, qh, kh, vt, kbias, n, Npad, dims.k_plane(),

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../kernels.h"
+#include "devmem.h"
 #include "model.h"
 
 namespace acemi {
@@ -25,7 +26,6 @@ struct BlockShape {
 class BlockRunner {
    public:
     BlockRunner();
-    ~BlockRunner();
     BlockRunner(const BlockRunner&) = delete;
     BlockRunner& operator=(const BlockRunner&) = delete;
     // the residual stream [rows][H] f32 (grown on demand; contents kept while the size fits)
@@ -42,18 +42,12 @@ class BlockRunner {
     void finish(const BlockShape& sh, const float* w, int B, int n, bool first_only, float* out, hipStream_t s);
 
    private:
-    struct Buf {
-        void* p = nullptr;
-        size_t bytes = 0;
-    };
-    void ensure(Buf& b, size_t bytes);
     template <typename T>
-    T* get(Buf& b) {
+    T* get(DevBuf& b) {
         return static_cast<T*>(b.p);
     }
-    Buf x_, act_, attn_, act2_, qkv_, qh_, kh_, vt_, kbias_, cos_, sin_;
-    int rope_n_ = -1;
-    float rope_theta_ = 0.f;
+    DevBuf x_, act_, attn_, act2_, qkv_, qh_, kh_, vt_, kbias_;
+    RopeTable rope_;  // positions 0..n-1 of each item
     bool split_ = true;  // hi/lo fp16 Q.K operands (ACE_MI_ATTN_PRECISION)
     bool pv_split_ = true;  // hi/lo fp16 P.V operands too
 };

@@ -36,8 +36,8 @@ void encode_host(ace_ggml_context* ctx, const acemi::DevEncoder* enc, const acem
     const size_t n_in = (size_t)B * n * proj.cols;
     const size_t n_out = (size_t)(first_only ? B : B * n) * H;
     const size_t o_out = (n_in * 4 + 255) & ~size_t(255);
-    ensure_dev(ctx->d_in, ctx->d_in_bytes, o_out + n_out * 4);
-    char* base = static_cast<char*>(ctx->d_in);
+    ctx->d_in.ensure(o_out + n_out * 4);
+    char* base = ctx->d_in.as<char>();
     ACEMI_HIP(hipMemcpyAsync(base, in, n_in * 4, hipMemcpyHostToDevice, s));
     acemi::EncodeIO io;
     io.enc = enc;

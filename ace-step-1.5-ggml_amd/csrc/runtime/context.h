@@ -25,16 +25,9 @@ struct ace_ggml_context {
     // ace_mi_load_lm: the causal LM with its KV cache (acemi::LmEngine, runtime/lm.cpp).  Type-erased so that only
     // lm.cpp, which holds the ace_mi_lm_* entries, refers to the engine and its decode kernels.
     std::shared_ptr<void> lm;
-    void* d_vae = nullptr;  // host-ABI staging for ace_ggml_vae_decode
-    size_t d_vae_bytes = 0;
-    // host-ABI staging (device)
-    void* d_in = nullptr;
-    size_t d_in_bytes = 0;
-    // sampler scratch
-    float* d_v = nullptr;
-    size_t d_v_bytes = 0;
-    float* d_sched = nullptr;
-    size_t d_sched_bytes = 0;
+    acemi::DevBuf d_vae;           // host-ABI staging for ace_ggml_vae_decode / ace_ggml_vae_encode
+    acemi::DevBuf d_in;            // host-ABI staging (device)
+    acemi::DevBuf d_v, d_sched;    // sampler scratch: the velocity, every step's timesteps
 };
 
 namespace acemi_abi {
@@ -73,17 +66,4 @@ inline void bind_device(ace_ggml_context* ctx) {
     ACEMI_HIP(hipSetDevice(ctx->device));
     if (!ctx->stream) ACEMI_HIP(hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking));
 }
-
-inline void ensure_dev(void*& p, size_t& have, size_t need) {
-    if (have >= need) return;
-    if (p) {
-        ACEMI_HIP(hipDeviceSynchronize());  // in-flight work may still use the old staging buffer
-        ACEMI_HIP(hipFree(p));
-    }
-    p = nullptr;
-    have = 0;
-    ACEMI_HIP(hipMalloc(&p, need));
-    have = need;
-}
-
 }  // namespace acemi_abi

@@ -32,7 +32,7 @@ DitEngine::DitEngine(int device) : device_(device) {
     if (!test_fault_from_env(fault_.layer, fault_.row, fault_.col, fault_.amp)) fault_.layer = -1;
 }
 
-DitEngine::~DitEngine() {  // (every Buf, and images_, frees itself)
+DitEngine::~DitEngine() {  // (every DevBuf, and images_, frees itself)
     if (pf_stream_) {
         (void)hipStreamSynchronize(pf_stream_);
         (void)hipStreamDestroy(pf_stream_);
@@ -157,37 +157,6 @@ void DitEngine::prepare_shape(int B, int Np, int L) {
     ensure(outmod_, (size_t)B * 2 * H * 4);
 }
 
-// NEOX RoPE table with the reference's own float arithmetic: ggml_rope_cache_init runs
-// theta = p; theta *= theta_scale per pair, theta_scale = powf(base, -2/n_dims), cos/sinf on the CPU
-// (acestep_dit_model.cpp:1205-1210).  Computed once per sequence length on the host.
-void DitEngine::rope_table(int n, Buf& cb, Buf& sb, hipStream_t s) {
-    const DitConfig& c = model_.cfg;
-    const int half = c.head_dim / 2;
-    const float theta_scale = powf(c.rope_theta, -2.0f / (float)c.head_dim);
-    std::vector<float> cs((size_t)n * half), sn((size_t)n * half);
-    for (int p = 0; p < n; ++p) {
-        float theta = (float)p;
-        for (int i = 0; i < half; ++i) {
-            cs[(size_t)p * half + i] = (float)std::cos((double)theta);  // correctly rounded cosf / sinf
-            sn[(size_t)p * half + i] = (float)std::sin((double)theta);
-            theta *= theta_scale;
-        }
-    }
-    // a forward still queued on `s` (a non-blocking stream) may read the old table: drain it first
-    ACEMI_HIP(hipStreamSynchronize(s));
-    ensure(cb, cs.size() * 4);
-    ensure(sb, sn.size() * 4);
-    ACEMI_HIP(hipMemcpy(cb.p, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
-    ACEMI_HIP(hipMemcpy(sb.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
-    ACEMI_HIP(hipDeviceSynchronize());  // null-stream copy: done before any stream reads it
-}
-
-void DitEngine::rope_for(int Np, hipStream_t s) {
-    if (rope_np_ == Np) return;
-    rope_table(Np, cos_, sin_, s);
-    rope_np_ = Np;
-}
-
 void DitEngine::forward(const ForwardIO& io, hipStream_t s) {
     if (qact_)
         walk<true>(io, s);
@@ -225,7 +194,7 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
         ACEMI_CHECK(kin == 1 && kout == 1,
                     "quantized-activation mode: F32 proj_in / proj_out (GGUF) are not supported");
     prepare_shape(B, Np, L);
-    rope_for(Np, s);
+    rope_.ensure(Np, c.head_dim, c.rope_theta, s);
     // parity: the cross K/V planes below are this mode's (f32 precision), not the cached ones
     if constexpr (QACT) cross_key_.valid = false;
 
@@ -402,7 +371,7 @@ void DitEngine::walk(const ForwardIO& io, hipStream_t s) {
         // self-attention block: the QKV projection with QK-RMSNorm, RoPE and the attention re-layout in its epilogue
         norm(at, ly.self_norm, scale_msa, shift_msa, mstride, act, false);
         project(lw[BW_QKV], qd + 2 * kd,
-                self_prep(dims, planes, nullptr, 0, ly.sq_norm, ly.sk_norm, get<float>(cos_), get<float>(sin_),
+                self_prep(dims, planes, nullptr, 0, ly.sq_norm, ly.sk_norm, rope_.cos(), rope_.sin(),
                           get<uint16_t>(qh_), get<uint16_t>(kh_), get<uint16_t>(vt_)),
                 "gemm_qkv");
         attention(get<uint16_t>(kh_), get<uint16_t>(vt_), io.mask ? get<float>(kbias_) : nullptr, Np, Npad,
@@ -580,8 +549,7 @@ void DitEngine::probe_gemm(int which, int M, int iters, hipStream_t s) {
 void DitEngine::free_lora() {
     images_.adapted.clear();
     images_.adapter_on = false;
-    if (lora_ab_) (void)hipFree(lora_ab_);
-    lora_ab_ = nullptr;
+    lora_ab_.release();
     lora_a_.clear();
     lora_b_.clear();
     lora_.reset();
@@ -677,7 +645,7 @@ void DitEngine::rebuild_lora_images(hipStream_t s) {
         for (const Slot& sl : mt.second) any = any || sl.mod >= 0;
         if (!any) continue;
         ACEMI_CHECK(w.q && w.fmt != WF_F32X3, "lora: the targeted weight is not a 16-bit or block-format matrix");
-        Buf& buf = images_.adapted[w.q];
+        DevBuf& buf = images_.adapted[w.q];
         ensure(buf, WeightImages::wbytes(w));
         uint16_t* img = static_cast<uint16_t*>(buf.p);
         const bool quantized = weight_quantized(w.fmt);
@@ -739,19 +707,19 @@ void DitEngine::load_lora(const std::string& dir, float scale, int max_layers, h
     auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
     for (const LoraModule& lm : ad->modules) total += al(lm.A.size() * 4) + al(lm.B.size() * 4);
     std::vector<char> host(total);
-    ACEMI_HIP(hipMalloc(&lora_ab_, total));
+    lora_ab_.ensure(total);
     size_t off = 0;
     for (LoraModule& lm : ad->modules) {
         std::memcpy(&host[off], lm.A.data(), lm.A.size() * 4);
-        lora_a_.push_back(reinterpret_cast<const float*>(static_cast<char*>(lora_ab_) + off));
+        lora_a_.push_back(reinterpret_cast<const float*>(lora_ab_.as<char>() + off));
         off += al(lm.A.size() * 4);
         std::memcpy(&host[off], lm.B.data(), lm.B.size() * 4);
-        lora_b_.push_back(reinterpret_cast<const float*>(static_cast<char*>(lora_ab_) + off));
+        lora_b_.push_back(reinterpret_cast<const float*>(lora_ab_.as<char>() + off));
         off += al(lm.B.size() * 4);
         lm.A = std::vector<float>();
         lm.B = std::vector<float>();
     }
-    ACEMI_HIP(hipMemcpy(lora_ab_, host.data(), total, hipMemcpyHostToDevice));
+    ACEMI_HIP(hipMemcpy(lora_ab_.p, host.data(), total, hipMemcpyHostToDevice));
     ACEMI_HIP(hipDeviceSynchronize());  // null-stream copy: done before any stream reads it
     lora_ = std::move(ad);
     lora_scale_ = scale;

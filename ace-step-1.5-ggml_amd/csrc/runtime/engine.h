@@ -131,37 +131,35 @@ class DitEngine {
 
    private:
     template <typename T>
-    T* get(Buf& b) {
+    T* get(DevBuf& b) {
         return static_cast<T*>(b.p);
     }
     void prepare_shape(int B, int Np, int L);
-    void rope_for(int Np, hipStream_t s);
     void tic(hipStream_t s);
     void toc(const char* name, hipStream_t s);
 
     int device_;
     DitModel model_;
     // workspace
-    Buf a0_, x_, act_, attn_, act2_, qkv_, qh_, kh_, vt_, kbias_, enc_act_, encp_, ckv_, kc_, vc_, kbias_c_;
-    Buf attn_part_;  // key-range split partials of the attention kernel (AttnArgs::part)
+    DevBuf a0_, x_, act_, attn_, act2_, qkv_, qh_, kh_, vt_, kbias_, enc_act_, encp_, ckv_, kc_, vc_, kbias_c_;
+    DevBuf attn_part_;  // key-range split partials of the attention kernel (AttnArgs::part)
     struct CrossKey {  // what kc_/vc_ currently hold (ForwardIO::reuse_cross)
         bool valid = false;
         int B = 0, L = 0, layers = 0;
         const float* enc = nullptr;
     } cross_key_;
-    Buf freq_, freq_act_, th_, th_act_, temb_t_, temb_r_, temb_act_, proj_, mods_, outmod_, cos_, sin_;
-    Buf ts_proj_, ts_temb_t_, ts_temb_r_;  // precompute_timesteps outputs
+    DevBuf freq_, freq_act_, th_, th_act_, temb_t_, temb_r_, temb_act_, proj_, mods_, outmod_;
+    DevBuf ts_proj_, ts_temb_t_, ts_temb_r_;  // precompute_timesteps outputs
     // timestep MLPs for rows items (t, r pointers per row): proj [rows][6H] (t and t - r summed), temb_t / temb_r
     // [rows][H]; freq_ / th_ serve as scratch for up to 8 rows at a time
     void timestep_embed(const float* t, const float* r, int rows, float* proj, float* temb_t, float* temb_r,
                         hipStream_t s);
-    int rope_np_ = -1;
-    Buf knorm_tab_;  // [layers] device pointers to the cross k-norm weights
+    RopeTable rope_;  // positions 0..Np-1 of the patch sequence
+    DevBuf knorm_tab_;  // [layers] device pointers to the cross k-norm weights
     size_t knorm_tab_n_ = 0;
     const float* const* cross_norm_table();
-    Buf ein_;             // condition-encoder input activations
+    DevBuf ein_;          // condition-encoder input activations
     BlockRunner cond_;    // condition-encoder blocks (own workspace: the DiT buffers stay untouched)
-    void rope_table(int n, Buf& cs, Buf& sn, hipStream_t s);
     bool attn_split_ = false;  // hi/lo fp16 Q.K operands (ACE_MI_ATTN_PRECISION)
     bool attn_pv_split_ = false;  // hi/lo fp16 P.V operands too
     bool attn_f8_ = false;        // f8c: the lo planes hold fp8 operands (AttnArgs::f8)
@@ -178,9 +176,9 @@ class DitEngine {
     // attention runs at the f32 precision -- the arithmetic of the reference's ggml graph.  A parity mode: the
     // product path keeps bf16 activations.
     bool qact_ = false;
-    Buf qf_, qa_, qs_, qb_, encf_;  // f32 activation rows, their int8 blocks, block scales / sums, f32 condition
-    Buf qa16_;                      // Q8_0 activation blocks as bf16(q) rows (the bf16-MFMA form, gemm_a8_bf16_path)
-    std::map<const void*, Buf> q8img_;  // bf16(q) image of each Q8_0 plane, made at its first q8-mode use
+    DevBuf qf_, qa_, qs_, qb_, encf_;  // f32 activation rows, their int8 blocks, block scales / sums, f32 condition
+    DevBuf qa16_;                      // Q8_0 activation blocks as bf16(q) rows (bf16-MFMA form, gemm_a8_bf16_path)
+    std::map<const void*, DevBuf> q8img_;  // bf16(q) image of each Q8_0 plane, made at its first q8-mode use
     const uint16_t* q8_image(const WeightView& w, int N, int K, hipStream_t s);
     void qlinear(const float* x, int64_t ldx, int M, const WeightView& w, int N, int K, const GemmEpilogue& e,
                  const char* name, hipStream_t s, bool silu_in = false);
@@ -192,7 +190,7 @@ class DitEngine {
     // images_, read while an adapter is loaded at a non-zero scale
     std::unique_ptr<LoraAdapter> lora_;
     std::vector<const float*> lora_a_, lora_b_;  // device A / B of lora_->modules[i]
-    void* lora_ab_ = nullptr;
+    DevBuf lora_ab_;
     float lora_scale_ = 0.f;
     double lora_merge_ms_ = 0.0;
     void rebuild_lora_images(hipStream_t s);
@@ -207,7 +205,7 @@ class DitEngine {
     int prefetch_blocks_ = 0;
     hipStream_t pf_stream_ = nullptr;
     hipEvent_t pf_ev_ = nullptr, pf_done_ = nullptr;
-    Buf pf_sink_;
+    DevBuf pf_sink_;
     void prefetch_layer(int li, hipStream_t s);
     // profiling
     bool profiling_ = false;

@@ -62,7 +62,7 @@ void DitEngine::qlinear(const float* x, int64_t ldx, int M, const WeightView& w,
 // bf16(q) image of a Q8_0 weight's int8 plane, made once on the stream that first needs it and kept while the model is
 // loaded (the engine is rebuilt with every load, so a plane pointer names one weight for the cache's lifetime)
 const uint16_t* DitEngine::q8_image(const WeightView& w, int N, int K, hipStream_t s) {
-    Buf& b = q8img_[w.q];
+    DevBuf& b = q8img_[w.q];
     if (!b.p) {
         ensure(b, (size_t)N * K * 2);
         launch_q8_image(static_cast<const int8_t*>(w.q), (int64_t)N * K, static_cast<uint16_t*>(b.p), s);

@@ -16,6 +16,7 @@
 #include "context.h"
 
 using namespace acemi_abi;
+using acemi::DevMem;
 
 namespace {
 
@@ -62,18 +63,6 @@ bool load_silence_latent(const char* path, int32_t seq_len, int32_t dim, std::ve
     }
     return true;
 }
-
-struct DevMem {
-    void* p = nullptr;
-    explicit DevMem(size_t n) { ACEMI_HIP(hipMalloc(&p, std::max<size_t>(n, 16))); }
-    ~DevMem() {
-        if (p) (void)hipFree(p);
-    }
-    template <typename T>
-    T* as() const {
-        return static_cast<T*>(p);
-    }
-};
 
 // ace_generate_audio_from_encoder (:1901-2238)
 ace_ggml_status generate_from_encoder(ace_ggml_context* ctx, const float* enc, const int32_t* enc_mask, int32_t enc_len,

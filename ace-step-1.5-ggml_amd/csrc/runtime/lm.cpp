@@ -25,45 +25,11 @@
 
 namespace acemi {
 
-namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    void ensure(size_t need) {
-        if (need == 0) need = 16;
-        if (bytes >= need) return;
-        release();
-        ACEMI_HIP(hipMalloc(&p, need));
-        bytes = need;
-    }
-    void release() {
-        if (!p) return;
-        (void)hipDeviceSynchronize();  // in-flight work may still use the buffer
-        (void)hipFree(p);
-        p = nullptr;
-        bytes = 0;
-    }
-    template <typename T>
-    T* as() const {
-        return static_cast<T*>(p);
-    }
-};
-
-}  // namespace
-
 // tokens between two host reads of the loop's stop word (ace_mi_lm_generate)
 constexpr int LM_STOP_POLL = 16;
 
 class LmEngine {
    public:
-    ~LmEngine() {
-        for (DevBuf* b : {&kc_, &vc_, &kmask_, &cos_, &sin_, &x_, &act_, &act2_, &qkv_, &q_, &attn_, &part_, &xn_, &xh_,
-                          &sel_work_, &sel_next_, &sel_done_, &sel_uni_})
-            b->release();
-        if (done_ev_) (void)hipEventDestroy(done_ev_);
-        free_pinned();
-    }
     TextModel& model() { return model_; }
     int batch() const { return batch_; }
     int capacity() const { return capacity_; }
@@ -96,24 +62,7 @@ class LmEngine {
         kc_.ensure(plane);
         vc_.ensure(plane);
         kmask_.ensure((size_t)B * cap * 4);
-        if (cap > rope_n_) {  // positions 0..cap-1, ggml's recurrence (BlockRunner::run builds the same values)
-            const int half = c.head_dim / 2;
-            const float theta_scale = powf(c.rope_theta, -2.0f / (float)c.head_dim);
-            std::vector<float> cs((size_t)cap * half), sn((size_t)cap * half);
-            for (int p = 0; p < cap; ++p) {
-                float theta = (float)p;
-                for (int i = 0; i < half; ++i) {
-                    cs[(size_t)p * half + i] = (float)std::cos((double)theta);
-                    sn[(size_t)p * half + i] = (float)std::sin((double)theta);
-                    theta *= theta_scale;
-                }
-            }
-            cos_.ensure(cs.size() * 4);
-            sin_.ensure(sn.size() * 4);
-            ACEMI_HIP(hipMemcpy(cos_.p, cs.data(), cs.size() * 4, hipMemcpyHostToDevice));
-            ACEMI_HIP(hipMemcpy(sin_.p, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
-            rope_n_ = cap;
-        }
+        rope_.ensure(cap, c.head_dim, c.rope_theta, nullptr);
         const int H = c.hidden, qd = c.hq * c.head_dim, kd = c.hkv * c.head_dim, I = c.intermediate;
         x_.ensure((size_t)LM_MAX_BATCH * H * 4);
         act_.ensure((size_t)LM_MAX_BATCH * std::max(H, qd) * 2);
@@ -124,7 +73,6 @@ class LmEngine {
         xn_.ensure((size_t)LM_MAX_BATCH * H * 4);
         xh_.ensure((size_t)LM_MAX_BATCH * H * 2);
         part_.ensure(lm_attn_part_floats(B, c.hq, cap) * 4);
-        ACEMI_HIP(hipDeviceSynchronize());  // null-stream copies: done before any stream reads them
         batch_ = B;
         capacity_ = cap;
         len_ = 0;
@@ -242,26 +190,30 @@ class LmEngine {
 
     // the `done` word of the loop through a pinned host word: async copy, event, wait
     int read_done(hipStream_t s) {
-        if (!pinned_) alloc_pinned();
-        if (!done_ev_) ACEMI_HIP(hipEventCreateWithFlags(&done_ev_, hipEventDisableTiming));
-        ACEMI_HIP(hipMemcpyAsync(pinned_, sel_done_.p, 4, hipMemcpyDeviceToHost, s));
-        ACEMI_HIP(hipEventRecord(done_ev_, s));
-        ACEMI_HIP(hipEventSynchronize(done_ev_));
-        return *pinned_;
+        if (!poll_.pinned) poll_.alloc();
+        if (!poll_.ev) ACEMI_HIP(hipEventCreateWithFlags(&poll_.ev, hipEventDisableTiming));
+        ACEMI_HIP(hipMemcpyAsync(poll_.pinned, sel_done_.p, 4, hipMemcpyDeviceToHost, s));
+        ACEMI_HIP(hipEventRecord(poll_.ev, s));
+        ACEMI_HIP(hipEventSynchronize(poll_.ev));
+        return *poll_.pinned;
     }
+    struct StopPoll {
+        int32_t* pinned = nullptr;
+        hipEvent_t ev = nullptr;
 #ifdef __HIP__
-    void alloc_pinned() { ACEMI_HIP(hipHostMalloc(reinterpret_cast<void**>(&pinned_), 16, hipHostMallocDefault)); }
-    void free_pinned() {
-        if (pinned_) (void)hipHostFree(pinned_);
-        pinned_ = nullptr;
-    }
+        void alloc() { ACEMI_HIP(hipHostMalloc(reinterpret_cast<void**>(&pinned), 16, hipHostMallocDefault)); }
+        ~StopPoll() {
+            if (ev) (void)hipEventDestroy(ev);
+            if (pinned) (void)hipHostFree(pinned);
+        }
 #else  // the host build has no pinned memory to ask for
-    void alloc_pinned() { pinned_ = static_cast<int32_t*>(std::calloc(4, 4)); }
-    void free_pinned() {
-        std::free(pinned_);
-        pinned_ = nullptr;
-    }
+        void alloc() { pinned = static_cast<int32_t*>(std::calloc(4, 4)); }
+        ~StopPoll() {
+            if (ev) (void)hipEventDestroy(ev);
+            std::free(pinned);
+        }
 #endif
+    };
 
     LmQkvPostArgs post_args(int li, const float* qkv, int ld) {
         const TextConfig& c = model_.cfg;
@@ -274,8 +226,8 @@ class LmEngine {
         a.hkv = c.hkv;
         a.q_norm = ly.sq_norm;
         a.k_norm = ly.sk_norm;
-        a.rope_cos = cos_.as<float>();
-        a.rope_sin = sin_.as<float>();
+        a.rope_cos = rope_.cos();
+        a.rope_sin = rope_.sin();
         a.eps = c.eps;
         a.q_out = q_.as<float>();
         a.k_cache = kc_.as<uint16_t>() + (size_t)li * layer;
@@ -378,11 +330,11 @@ class LmEngine {
 
     TextModel model_;
     BlockRunner blocks_;
-    DevBuf kc_, vc_, kmask_, cos_, sin_, x_, act_, act2_, qkv_, q_, attn_, part_, xn_, xh_;
+    StopPoll poll_;  // declared before the buffers: the event and the pinned word go after the buffers are freed
+    DevBuf kc_, vc_, kmask_, x_, act_, act2_, qkv_, q_, attn_, part_, xn_, xh_;
     DevBuf sel_work_, sel_next_, sel_done_, sel_uni_;  // selection scratch, the next step's ids, the stop words, uniforms
-    int32_t* pinned_ = nullptr;
-    hipEvent_t done_ev_ = nullptr;
-    int batch_ = 0, capacity_ = 0, len_ = 0, rope_n_ = 0;
+    RopeTable rope_;  // positions 0..capacity-1
+    int batch_ = 0, capacity_ = 0, len_ = 0;
 };
 
 }  // namespace acemi
@@ -436,7 +388,7 @@ ace_ggml_status ace_mi_lm_get_info(ace_ggml_context* ctx, ace_mi_lm_info* out) {
     out->batch = e->batch();
     out->capacity = e->capacity();
     out->cache_len = e->len();
-    out->weight_bytes = (int64_t)e->model().weight_bytes;
+    out->weight_bytes = (int64_t)e->model().arena.bytes();
     out->cache_bytes = (int64_t)e->cache_bytes();
     return ACE_GGML_OK;
 }

@@ -9,6 +9,7 @@
 #include <utility>
 #include <vector>
 
+#include "devmem.h"
 #include "gguf.h"
 #include "model.h"
 #include "quant.h"
@@ -68,8 +69,7 @@ inline uint16_t f32_to_f16_host(float f) {
 }
 
 struct Loader {
-    std::vector<void*>& allocs;  // device allocations of the model being loaded (freed by its owner)
-    size_t& weight_bytes;
+    DevArena& arena;  // device allocations of the model being loaded (freed by its owner)
     StFile st;
     GgufFile gg;
     bool gguf = false;
@@ -80,18 +80,8 @@ struct Loader {
     bool raw_to_image = false;
     std::string first_raw_name;  // first tensor kept as raw blocks, and its ggml type (the q8 mode's refusal)
     int first_raw_type = -1;
-    Loader(std::vector<void*>& a, size_t& wb) : allocs(a), weight_bytes(wb) {}
+    explicit Loader(DevArena& a) : arena(a) {}
 
-    template <typename T>
-    T* upload(const void* host, size_t bytes) {
-        void* d = nullptr;
-        ACEMI_HIP(hipMalloc(&d, bytes));
-        allocs.push_back(d);
-        ACEMI_HIP(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
-        ACEMI_HIP(hipDeviceSynchronize());  // null-stream copy: done before any stream reads it
-        weight_bytes += bytes;
-        return static_cast<T*>(d);
-    }
     // F32 / F16 / BF16 tensor -> f32 values (read_gguf_tensor_as_f32, acestep_dit_model.cpp:554-600)
     std::vector<float> gguf_f32(const GgufTensor& t) {
         auto raw = gg.read(t);
@@ -129,7 +119,7 @@ struct Loader {
             v = to_f32(t, st.read(t));
         }
         if (expect >= 0 && (int64_t)v.size() != expect) throw IoError("invalid tensor shape for " + name);
-        return upload<float>(v.data(), v.size() * 4);
+        return arena.upload<float>(v.data(), v.size() * 4);
     }
     // matrix [rows][cols] (2-D, or 3-D flattened over the last two dims)
     Mat mat(const std::string& name, int64_t rows, int64_t cols) {
@@ -333,8 +323,8 @@ struct Loader {
         std::vector<float> sp(quant::s_plane_floats(q, rows, cols));
         quant::to_planes(q, blocks, rows, cols, qp.data(), sp.data());
         w.fmt = q == quant::Q8_0 ? WF_Q8_0 : (q == quant::Q4_K ? WF_Q4_K : WF_Q6_K);
-        w.q = upload<uint8_t>(qp.data(), qp.size());
-        w.s = upload<float>(sp.data(), sp.size() * 4);
+        w.q = arena.upload<uint8_t>(qp.data(), qp.size());
+        w.s = arena.upload<float>(sp.data(), sp.size() * 4);
         return w;
     }
     // Raw block rows: the file's bytes in one allocation (each segment 16-byte aligned, 16 readable bytes after the
@@ -356,7 +346,7 @@ struct Loader {
             offs.push_back(off);
             off += (p.bytes.size() + 15) & ~size_t(15);
         }
-        uint8_t* base = upload<uint8_t>(host.data(), host.size());
+        uint8_t* base = arena.upload<uint8_t>(host.data(), host.size());
         for (size_t i = 0; i < a.parts.size(); ++i) {
             const RawPart& p = a.parts[i];
             BlockSeg g;
@@ -377,22 +367,12 @@ struct Loader {
             }
             return w;
         }
-        void* img = nullptr;
-        ACEMI_HIP(hipMalloc(&img, (size_t)a.rows * a.cols * 2));
+        void* img = arena.alloc((size_t)a.rows * a.cols * 2);
         std::vector<DequantBlocksJob> jobs;
         for (const BlockSeg& g : w.segs) jobs.push_back(DequantBlocksJob{g, w.cols, w.cols, static_cast<uint16_t*>(img)});
-        try {
-            launch_dequant_blocks(jobs.data(), (int)jobs.size(), nullptr);
-            ACEMI_HIP(hipDeviceSynchronize());
-        } catch (...) {
-            (void)hipFree(img);
-            throw;
-        }
-        allocs.pop_back();  // the blocks (the upload above)
-        (void)hipFree(base);
-        weight_bytes -= host.size();
-        allocs.push_back(img);
-        weight_bytes += (size_t)a.rows * a.cols * 2;
+        launch_dequant_blocks(jobs.data(), (int)jobs.size(), nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        arena.drop_before_last();  // the blocks (the upload above); the image stays
         DevWeight d;
         d.rows = w.rows;
         d.cols = w.cols;
@@ -420,7 +400,7 @@ struct Loader {
                 row[a.cols + c] = lo;
                 row[2 * a.cols + c] = hi;
             }
-        w.q = upload<uint16_t>(h.data(), h.size() * 2);
+        w.q = arena.upload<uint16_t>(h.data(), h.size() * 2);
         return w;
     }
     // try_quantize_matrix (acestep_dit_model.cpp:156-192): quantize when requested and in-dim % block == 0
@@ -443,7 +423,7 @@ struct Loader {
         w.rows = static_cast<int>(a.rows);
         w.cols = static_cast<int>(a.cols);
         w.fmt = a.dtype == "F16" ? WF_F16 : WF_BF16;
-        w.q = upload<uint16_t>(a.u16.data(), a.u16.size() * 2);
+        w.q = arena.upload<uint16_t>(a.u16.data(), a.u16.size() * 2);
         return w;
     }
     // dense 16-bit copy for the GEMV path: the file bits, or bf16(dequant(q)) for quantized weights
@@ -458,10 +438,10 @@ struct Loader {
             std::vector<uint16_t> b(v.size());
             for (size_t i = 0; i < v.size(); ++i) b[i] = f32_to_bf16_host(v[i]);
             act = ActType::BF16;
-            return upload<uint16_t>(b.data(), b.size() * 2);
+            return arena.upload<uint16_t>(b.data(), b.size() * 2);
         }
         act = a.dtype == "F16" ? ActType::F16 : ActType::BF16;
-        return upload<uint16_t>(a.u16.data(), a.u16.size() * 2);
+        return arena.upload<uint16_t>(a.u16.data(), a.u16.size() * 2);
     }
     // mlp.gate_proj | mlp.up_proj as one [2I][H] weight, rows interleaved in groups of 16
     // ([g0..15, u0..15, g16..31, ...]) for the SwiGLU epilogue

@@ -15,10 +15,6 @@
 
 namespace acemi {
 
-DitModel::~DitModel() {
-    for (void* p : allocs) (void)hipFree(p);
-}
-
 bool quant_act_from_env() {
     const char* e = std::getenv("ACE_MI_QUANT_ACT");
     if (!e || !e[0] || std::strcmp(e, "bf16") == 0) return false;
@@ -136,7 +132,7 @@ void load_dit_model(const std::string& dir, DitModel& m, int& status_hint) {
         if ((c.patch * c.in_channels) % 64 != 0) throw Unsupported("patch*in_channels must be a multiple of 64");
         if ((c.patch * c.audio_dim) % 128 != 0) throw Unsupported("patch*audio_dim must be a multiple of 128");
 
-        Loader L(m.allocs, m.weight_bytes);
+        Loader L(m.arena);
         L.qt = qt;
         m.qtype = qt;
         if (!gguf_path.empty()) {
@@ -188,7 +184,7 @@ void load_dit_model(const std::string& dir, DitModel& m, int& status_hint) {
         m.norm_out = L.vec_f32("decoder.norm_out.weight", H);
         {
             auto ot = L.table("decoder.scale_shift_table", 2, H);
-            m.out_table = L.upload<float>(ot.data(), ot.size() * 4);
+            m.out_table = L.arena.upload<float>(ot.data(), ot.size() * 4);
         }
         const char* tags[2] = {"decoder.time_embed.", "decoder.time_embed_r."};
         for (int e = 0; e < 2; ++e) {
@@ -254,7 +250,7 @@ void load_dit_model(const std::string& dir, DitModel& m, int& status_hint) {
             }
             ly.sliding = i < (int)c.layer_types.size() && c.layer_types[i] == "sliding_attention";
         }
-        m.tables = L.upload<float>(tables.data(), tables.size() * 4);
+        m.tables = L.arena.upload<float>(tables.data(), tables.size() * 4);
         // every layer's cross k|v in one [layers*2kd][H] matrix when they share a type (always, except a
         // GGUF file mixing types across layers): the encoder-side projections become one GEMM with
         // N = layers*2kd instead of `layers` GEMMs of M = L rows that fill a quarter of the GPU

@@ -16,6 +16,7 @@
 
 #include "../common.h"
 #include "../kernels.h"
+#include "devmem.h"
 
 namespace acemi {
 
@@ -130,10 +131,7 @@ struct DitModel {
     // condition encoders (optional tensors; acestep_dit_model.cpp:885-996)
     DevWeight text_proj;             // encoder.text_projector.weight [H][text_hidden] (no bias)
     DevEncoder lyric, timbre;
-    std::vector<void*> allocs;
-    size_t weight_bytes = 0;
-
-    ~DitModel();
+    DevArena arena;  // every device allocation above
 };
 
 // ACE_MI_QUANT_ACT=q8: the ggml-faithful quantized-activation mode (DitEngine::walk<true>); anything else (the

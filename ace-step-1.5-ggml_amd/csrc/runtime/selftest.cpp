@@ -11,23 +11,10 @@
 #include "../../../include/acestep_mi355x_selftest.h"
 #include "../gemm_variants.h"
 #include "../kernels.h"
+#include "devmem.h"
 #include "quant.h"
 
-namespace {
-
-struct DevMem {
-    void* p = nullptr;
-    explicit DevMem(size_t bytes) { ACEMI_HIP(hipMalloc(&p, bytes ? bytes : 16)); }
-    ~DevMem() {
-        if (p) (void)hipFree(p);
-    }
-    template <typename T>
-    T* as() {
-        return static_cast<T*>(p);
-    }
-};
-
-}  // namespace
+using acemi::DevMem;
 
 extern "C" {
 
@@ -1055,6 +1042,35 @@ ace_ggml_status ace_mi_kernel_pack_f16(const float* x, int64_t rows, int32_t C, 
         return ACE_GGML_ERR;
     }
     return ACE_GGML_OK;
+}
+
+// ---- the RoPE table (runtime/devmem.h), without a kernel
+ace_ggml_status ace_mi_rope_table_steps(int32_t steps, const int32_t* n, const int32_t* head_dim, const float* theta,
+                                        int32_t* rows, float* cos_out, float* sin_out) {
+    if (steps < 1 || !n || !head_dim || !theta || !rows || !cos_out || !sin_out) return ACE_GGML_ERR_INVALID_ARG;
+    for (int i = 0; i < steps; ++i)
+        if (n[i] < 1 || n[i] > (1 << 20) || head_dim[i] < 2 || head_dim[i] > 1024 || head_dim[i] % 2 != 0 ||
+            !(theta[i] > 0.0f))
+            return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        acemi::RopeTable t;
+        for (int i = 0; i < steps; ++i) {
+            t.ensure(n[i], head_dim[i], theta[i], nullptr);
+            rows[i] = t.rows();
+        }
+        const size_t bytes = (size_t)t.rows() * (head_dim[steps - 1] / 2) * 4;
+        ACEMI_HIP(hipMemcpy(cos_out, t.cos(), bytes, hipMemcpyDeviceToHost));
+        ACEMI_HIP(hipMemcpy(sin_out, t.sin(), bytes, hipMemcpyDeviceToHost));
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_rope_table: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_rope_table(int32_t n, int32_t head_dim, float theta, float* cos_out, float* sin_out) {
+    int32_t rows = 0;
+    return ace_mi_rope_table_steps(1, &n, &head_dim, &theta, &rows, cos_out, sin_out);
 }
 
 }  // extern "C"

@@ -10,27 +10,12 @@
 
 #include "../../../include/acestep_mi355x_selftest.h"
 #include "../kernels.h"
+#include "devmem.h"
 #include "quant.h"
 
 namespace {
 
-struct DevMem {
-    void* p = nullptr;
-    explicit DevMem(size_t bytes) { ACEMI_HIP(hipMalloc(&p, bytes ? bytes : 16)); }
-    DevMem(const void* host, size_t bytes) : DevMem(bytes) {
-        if (host) ACEMI_HIP(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
-    }
-    ~DevMem() {
-        if (p) (void)hipFree(p);
-    }
-    DevMem(const DevMem&) = delete;
-    DevMem& operator=(const DevMem&) = delete;
-    template <typename T>
-    T* as() {
-        return static_cast<T*>(p);
-    }
-    void to_host(void* host, size_t bytes) { ACEMI_HIP(hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost)); }
-};
+using acemi::DevMem;
 
 constexpr int D = 128;
 

@@ -47,8 +47,8 @@ ace_ggml_status run_text(ace_ggml_context* ctx, const int32_t* ids, const int32_
         hipStream_t s = ctx->stream;
         // staging: ids | mask | out
         const size_t o_mask = ((size_t)n * 4 + 255) & ~size_t(255), o_out = o_mask + o_mask;
-        ensure_dev(ctx->d_in, ctx->d_in_bytes, o_out + needed);
-        char* base = static_cast<char*>(ctx->d_in);
+        ctx->d_in.ensure(o_out + needed);
+        char* base = ctx->d_in.as<char>();
         ACEMI_HIP(hipMemcpyAsync(base, ids, (size_t)n * 4, hipMemcpyHostToDevice, s));
         const int32_t* d_mask = nullptr;
         if (mask) {

@@ -10,10 +10,6 @@
 
 namespace acemi {
 
-TextModel::~TextModel() {
-    for (void* p : allocs) (void)hipFree(p);
-}
-
 namespace {
 
 void load_text_config(const std::string& path, TextConfig& c) {  // qwen_config.cpp:19-64
@@ -87,7 +83,7 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
     if (rep != 1 && rep != 2 && rep != 4) throw Unsupported("GQA ratio must be 1, 2 or 4");
     if (c.vocab <= 0 || c.layers < 0) throw IoError("invalid text encoder config");
 
-    Loader L(m.allocs, m.weight_bytes);
+    Loader L(m.arena);
     // get_quant_type_from_env (qwen_model.cpp:38-44); the GGUF loaders keep the file's types
     L.qt = gguf_path.empty() ? quant::from_env("ACE_GGML_QWEN_WEIGHT_QTYPE") : quant::QNONE;
     m.qtype = L.qt;
@@ -121,7 +117,7 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
         } else if (e.dtype == "BF16" || e.dtype == "F16") {
             if (!quant::applies(L.qt, H)) {
                 m.embed_fmt = e.dtype == "BF16" ? 0 : 1;
-                m.embed = L.upload<uint16_t>(e.u16.data(), e.u16.size() * 2);
+                m.embed = L.arena.upload<uint16_t>(e.u16.data(), e.u16.size() * 2);
             }
         }
         if (!m.embed && m.embed_fmt != 3 && opt.lm_checkpoint && !L.gguf)
@@ -134,7 +130,7 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
                 quant::dequantize_rows(L.qt, blocks.data(), c.vocab, H, v.data());
             }
             m.embed_fmt = 2;
-            m.embed = L.upload<float>(v.data(), v.size() * 4);
+            m.embed = L.arena.upload<float>(v.data(), v.size() * 4);
         }
         if (opt.lm_head && !L.has("lm_head.weight") && c.tie_word_embeddings != 0) {  // the tied head: the table itself
             if (m.embed_fmt == 3) {
@@ -175,7 +171,7 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
         const Mat hw = L.mat("lm_head.weight", c.vocab, H);
         if (hw.dtype == "BF16" || hw.dtype == "F16") {  // its own 16-bit type: the head rounds its input itself
             m.head.fmt = hw.dtype == "F16" ? WF_F16 : WF_BF16;
-            m.head.q = L.upload<uint16_t>(hw.u16.data(), hw.u16.size() * 2);
+            m.head.q = L.arena.upload<uint16_t>(hw.u16.data(), hw.u16.size() * 2);
             m.head.rows = c.vocab;
             m.head.cols = H;
         } else if (hw.dtype == "Q" || hw.dtype == "R") {

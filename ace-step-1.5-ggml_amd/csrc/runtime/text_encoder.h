@@ -32,9 +32,7 @@ struct TextModel {
     // Loader::finish gives a matrix (dense 16-bit, block planes, bf16 image); tied: the table's own allocation
     DevWeight head;
     bool tied = false;
-    std::vector<void*> allocs;
-    size_t weight_bytes = 0;
-    ~TextModel();
+    DevArena arena;  // every device allocation above
 };
 
 // What ace_mi_load_lm asks of the loader beyond the text encoder's behaviour (all off = ace_ggml_load_text_encoder /

@@ -24,16 +24,6 @@ struct VaeLoader {
     StFile st;
     explicit VaeLoader(VaeModel& mm) : m(mm) {}
 
-    template <typename T>
-    T* upload(const void* host, size_t bytes) {
-        void* d = nullptr;
-        ACEMI_HIP(hipMalloc(&d, bytes));
-        m.allocs.push_back(d);
-        ACEMI_HIP(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
-        ACEMI_HIP(hipDeviceSynchronize());  // null-stream copy: done before any stream reads it
-        m.weight_bytes += bytes;
-        return static_cast<T*>(d);
-    }
     std::vector<float> tensor(const std::string& name, std::vector<int64_t>& shape) {
         const auto& t = st.get(name);
         shape = t.shape;
@@ -48,7 +38,7 @@ struct VaeLoader {
             auto v = tensor(prefix + (which ? ".beta" : ".alpha"), sh);
             if ((int64_t)v.size() != C) throw IoError("invalid tensor shape for " + prefix);
             for (auto& x : v) x = expf(x);
-            (which ? s.eb : s.ea) = upload<float>(v.data(), v.size() * 4);
+            (which ? s.eb : s.ea) = m.arena.upload<float>(v.data(), v.size() * 4);
         }
         return s;
     }
@@ -73,7 +63,7 @@ struct VaeLoader {
         std::vector<int64_t> sh;
         auto b = tensor(prefix + ".bias", sh);
         if ((int64_t)b.size() != cout) throw IoError("invalid tensor shape for " + prefix + ".bias");
-        return upload<float>(b.data(), b.size() * 4);
+        return m.arena.upload<float>(b.data(), b.size() * 4);
     }
     // ggml_conv_1d weight [Cout][Cin][K] -> W [Cout][K][Cin_pad] fp16 (zero columns past Cin)
     VaeConv conv(const std::string& prefix, bool with_bias, int dil, int pad, int stride = 1, int cin_pad_to = 1) {
@@ -93,7 +83,7 @@ struct VaeLoader {
                 for (int k = 0; k < c.taps; ++k)
                     h[((size_t)co * c.taps + k) * c.cin + ci] =
                         f32_to_f16_bits(w[((size_t)co * c.cin_real + ci) * c.taps + k]);
-        c.w = upload<uint16_t>(h.data(), h.size() * 2);
+        c.w = m.arena.upload<uint16_t>(h.data(), h.size() * 2);
         if (with_bias) c.b = bias(prefix, c.cout);
         return c;
     }
@@ -116,7 +106,7 @@ struct VaeLoader {
                     for (int ci = 0; ci < c.cin; ++ci)
                         h[((size_t)(r * c.cout + co) * 2 + tap) * c.cin + ci] =
                             f32_to_f16_bits(w[((size_t)ci * c.cout + co) * (2 * stride) + r + tap * stride]);
-        c.w = upload<uint16_t>(h.data(), h.size() * 2);
+        c.w = m.arena.upload<uint16_t>(h.data(), h.size() * 2);
         c.b = bias(prefix, c.cout);
         return c;
     }
@@ -129,10 +119,6 @@ void check_gemm_conv(const VaeConv& c, const std::string& what) {
 }
 
 }  // namespace
-
-VaeModel::~VaeModel() {
-    for (void* p : allocs) (void)hipFree(p);
-}
 
 void load_vae_model(const std::string& dir, VaeModel& m, int& status_hint) {
     status_hint = 3;
@@ -278,29 +264,6 @@ void load_vae_model(const std::string& dir, VaeModel& m, int& status_hint) {
     }
 }
 
-VaeEngine::~VaeEngine() {
-    for (Buf* b : {&x_, &sa_, &sb_, &sc_, &lat_, &zero_})
-        if (b->p) (void)hipFree(b->p);
-}
-
-void VaeEngine::ensure(Buf& b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return;
-    if (b.p) {
-        ACEMI_HIP(hipDeviceSynchronize());
-        ACEMI_HIP(hipFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
-    }
-    const size_t alloc = (bytes + 255) & ~size_t(255);
-    ACEMI_HIP(hipMalloc(&b.p, alloc));
-    ACEMI_HIP(hipMemset(b.p, 0, alloc));
-    // hipMemset runs on the legacy null stream, which does not order against the library's
-    // non-blocking streams: finish it before any kernel can write the new buffer
-    ACEMI_HIP(hipDeviceSynchronize());
-    b.bytes = alloc;
-}
-
 int64_t VaeEngine::out_len(int n_frames) const {
     int64_t L = n_frames;
     for (const auto& b : model_.blocks) {
@@ -406,7 +369,7 @@ void VaeEngine::decode(const float* d_latents, int n_frames, float* d_out, hipSt
     ensure(sb_, (size_t)maxe * 2);
     ensure(sc_, (size_t)maxe * 2);
     ensure(lat_, (size_t)items * n_frames * m.conv1.cin * 2);
-    ensure(zero_, 4096);  // >= 64 fp16 zeros (hipMemset in ensure())
+    ensure(zero_, 4096);  // >= 64 fp16 zeros (DevBuf::ensure zero-fills)
 
     float* X = static_cast<float*>(x_.p);
     uint16_t* Sa = static_cast<uint16_t*>(sa_.p);

@@ -15,6 +15,7 @@
 
 #include "../common.h"
 #include "../kernels.h"
+#include "devmem.h"
 
 namespace acemi {
 
@@ -68,9 +69,7 @@ struct VaeModel {
     std::vector<VaeEncBlock> enc_blocks;
     VaeSnake enc_snake1;
     VaeConv enc_conv2;
-    std::vector<void*> allocs;
-    size_t weight_bytes = 0;
-    ~VaeModel();
+    DevArena arena;  // every device allocation above
 };
 
 // Throws std::runtime_error; status_hint 3 (IO) / 4 (UNSUPPORTED) / 1 (ERR).
@@ -84,7 +83,6 @@ public:
         // TEST ONLY (self-test library builds): ACE_MI_TEST_VAE_FAULT, runtime/test_hooks.cpp
         if (!test_vae_fault_from_env(fault_.block, fault_.row, fault_.col, fault_.amp)) fault_.block = -1;
     }
-    ~VaeEngine();
     VaeModel& model() { return model_; }
     int device() const { return device_; }
     // samples produced for n_frames latent frames (= n_frames * hop for even strides; PyTorch
@@ -100,14 +98,9 @@ public:
     void encode(const float* d_audio, int n_samples, float* d_out, hipStream_t s);
 
 private:
-    struct Buf {
-        void* p = nullptr;
-        size_t bytes = 0;
-    };
-    void ensure(Buf& b, size_t bytes);
     int device_;
     VaeModel model_;
-    Buf x_, sa_, sb_, sc_, lat_, zero_;
+    DevBuf x_, sa_, sb_, sc_, lat_, zero_;
     int items_ = 1;  // sequences per conv launch during decode (ConvGemmArgs::items)
     // 128-channel residual units as one launch (ConvGemmArgs::W2); ACE_MI_VAE_FUSE_RES=0: two launches
     bool fuse_res_ = true;

@@ -21,37 +21,10 @@
 #include <map>
 
 #include "../kernels.h"
+#include "devmem.h"
 #include "model.h"
 
 namespace acemi {
-
-// A device allocation that only grows; not copied.
-struct Buf {
-    void* p = nullptr;
-    size_t bytes = 0;
-    Buf() = default;
-    Buf(Buf&&) = delete;
-    ~Buf() {
-        if (p) (void)hipFree(p);
-    }
-};
-inline void ensure(Buf& b, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (b.bytes >= bytes) return;
-    if (b.p) {
-        ACEMI_HIP(hipDeviceSynchronize());
-        ACEMI_HIP(hipFree(b.p));
-        b.p = nullptr;
-        b.bytes = 0;
-    }
-    const size_t alloc = (bytes + 255) & ~size_t(255);
-    ACEMI_HIP(hipMalloc(&b.p, alloc));
-    ACEMI_HIP(hipMemset(b.p, 0, alloc));
-    // hipMemset runs on the legacy null stream, which does not order against the library's
-    // non-blocking streams: finish it before any kernel can write the new buffer
-    ACEMI_HIP(hipDeviceSynchronize());
-    b.bytes = alloc;
-}
 
 enum class StageScope { Model, Call, Layer };
 using LayerViews = std::array<WeightView, N_BLOCK_WEIGHTS>;  // indexed by BlockWeight
@@ -129,7 +102,7 @@ class WeightImages {
     WeightView matrix(const DevWeight& w, hipStream_t s) {
         Pick r = resolve(w, false, nullptr);
         if (!r.image) return r.v;
-        Buf& b = kept_[w.q];
+        DevBuf& b = kept_[w.q];
         if (!b.p) {
             ensure(b, wbytes(w));
             expand(w, static_cast<uint16_t*>(b.p), s);
@@ -143,7 +116,7 @@ class WeightImages {
 
     // Adapted images, keyed by the resident weight pointer: the LoRA code allocates (ensure) and writes them, and
     // resolve() reads them while adapter_on.  expand: the bf16 image of a quantized w, the base of its merge.
-    std::map<const void*, Buf> adapted;
+    std::map<const void*, DevBuf> adapted;
     bool adapter_on = false;
     static void expand(const DevWeight& w, uint16_t* out, hipStream_t s) {
         Expander e;
@@ -213,11 +186,11 @@ class WeightImages {
     bool staged_quant_ = true;
     // this forward (begin_forward): the layer loop reads arena slots / expands them first; an image was written
     bool arena_on_ = false, expand_ = false, wrote_ = false;
-    Buf arena_;  // one slot per layer, or the one shared slot of the layer scope; allocated once something is staged
+    DevBuf arena_;  // one slot per layer, or the one shared slot of the layer scope; allocated once something is staged
     size_t slot_bytes_ = 0;
-    int kept_layers_ = 0;               // layers whose slots hold their images (model / call scope)
-    std::map<const void*, Buf> kept_;   // keyed by the resident weight pointer
-    hipEvent_t ev_ = nullptr;           // created and recorded after a forward that wrote images
+    int kept_layers_ = 0;                  // layers whose slots hold their images (model / call scope)
+    std::map<const void*, DevBuf> kept_;   // keyed by the resident weight pointer
+    hipEvent_t ev_ = nullptr;              // created and recorded after a forward that wrote images
 };
 
 }  // namespace acemi

@@ -257,6 +257,17 @@ ACE_GGML_API ace_ggml_status ace_mi_gemm_resolve(int32_t forced, int32_t overrid
 ACE_GGML_API ace_ggml_status ace_mi_gemm_variant_row(int32_t id, int32_t fields[16], char* name, size_t name_size);
 ACE_GGML_API ace_ggml_status ace_mi_gemm_variant_arg_ok(int32_t variant, int32_t allow_unchecked);
 
+/* The NEOX RoPE table every engine reads (csrc/runtime/devmem.h, RopeTable), built and copied back: cos_out and
+ * sin_out [n][head_dim / 2] f32, positions 0..n-1.
+ * ace_mi_rope_table_steps: `steps` ensure(n[i], head_dim[i], theta[i]) calls in a row on one table; rows[i] = the rows
+ * the table holds after call i, and cos_out / sin_out receive the final table, rows[steps - 1] rows of
+ * head_dim[steps - 1] / 2 values (the caller sizes them for that). */
+ACE_GGML_API ace_ggml_status ace_mi_rope_table(int32_t n, int32_t head_dim, float theta, float* cos_out,
+                                               float* sin_out);
+ACE_GGML_API ace_ggml_status ace_mi_rope_table_steps(int32_t steps, const int32_t* n, const int32_t* head_dim,
+                                                     const float* theta, int32_t* rows, float* cos_out,
+                                                     float* sin_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,10 +7,13 @@
 // usage: asan_driver <dit_cond_dir> <vae_dir> <text_dir> <dit_gguf_dir> [<malformed_dit_dir>...]
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <map>
 #include <random>
 #include <vector>
 
 #include "../../include/acestep_mi355x.h"
+#include "runtime/devmem.h"
 
 static int failures = 0;
 #define EXPECT(cond)                                                      \
@@ -29,8 +32,80 @@ static std::vector<float> randn(size_t n, unsigned seed) {
     return v;
 }
 
+// The owners of runtime/devmem.h on their own: grow, move, release, the arena's replacement, the RoPE table's prefix
+// rule.  Leak detection is on, so an allocation that a move or a destructor forgets is reported, like a double free.
+static void devmem_owners() {
+    using namespace acemi;
+    DevBuf a;
+    a.ensure(0);
+    EXPECT(a.p && a.bytes == 256);
+    void* first = a.p;
+    a.ensure(100);
+    EXPECT(a.p == first && a.bytes == 256);  // large enough: untouched
+    std::memset(a.p, 0xff, a.bytes);
+    a.ensure(1000);
+    EXPECT(a.bytes == 1024);
+    for (size_t i = 0; i < a.bytes; ++i) EXPECT(a.as<unsigned char>()[i] == 0);  // regrown: zero-filled, all of it
+    DevBuf b(std::move(a));
+    EXPECT(!a.p && a.bytes == 0 && b.p && b.bytes == 1024);
+    DevBuf c;
+    c.ensure(300);
+    c = std::move(b);  // frees c's 512 bytes
+    EXPECT(!b.p && b.bytes == 0 && c.bytes == 1024);
+    c.release();
+    c.release();
+    EXPECT(!c.p && c.bytes == 0);
+    c.ensure(17);  // usable again after a release
+    EXPECT(c.bytes == 256);
+    a.ensure(40);  // and a moved-from one
+    std::map<int, DevBuf> m;
+    m[1].ensure(64);
+    m[2].ensure(64);
+    m.erase(1);
+
+    unsigned char src[100], back[100] = {};
+    for (int i = 0; i < 100; ++i) src[i] = (unsigned char)(i * 7);
+    DevMem up(src, sizeof(src)), none(nullptr, 0), plain(3);
+    up.to_host(back, sizeof(back));
+    EXPECT(std::memcmp(src, back, sizeof(src)) == 0);
+    std::memset(none.p, 1, 16);  // the 16-byte minimum
+    std::memset(plain.p, 1, 16);
+
+    DevArena ar;
+    EXPECT(ar.bytes() == 0);
+    bool threw = false;
+    try {
+        ar.drop_before_last();
+    } catch (const std::exception&) {
+        threw = true;
+    }
+    EXPECT(threw);
+    unsigned char* keep = ar.upload<unsigned char>(src, 100);
+    ar.upload<unsigned char>(src, 60);  // the blocks an image replaces
+    void* img = ar.alloc(200);
+    std::memset(img, 2, 200);
+    ar.drop_before_last();
+    EXPECT(ar.bytes() == 300);
+    EXPECT(std::memcmp(keep, src, 100) == 0 && static_cast<unsigned char*>(img)[199] == 2);
+    ar.upload<unsigned char>(src, 10);
+    EXPECT(ar.bytes() == 310);
+
+    RopeTable t;
+    t.ensure(40, 128, 1e6f, nullptr);
+    const float* table = t.cos();
+    const float c39 = t.cos()[39 * 64 + 63], s39 = t.sin()[39 * 64 + 1];
+    t.ensure(17, 128, 1e6f, nullptr);
+    EXPECT(t.rows() == 40 && t.cos() == table && t.cos()[39 * 64 + 63] == c39);  // the longer table stays
+    t.ensure(200, 128, 1e6f, nullptr);
+    EXPECT(t.rows() == 200 && t.cos()[39 * 64 + 63] == c39 && t.sin()[39 * 64 + 1] == s39);
+    EXPECT(t.cos()[199 * 64 + 63] != 0.f || t.sin()[199 * 64 + 63] != 0.f);
+    t.ensure(9, 64, 1e4f, nullptr);
+    EXPECT(t.rows() == 9 && t.sin()[8 * 32 + 1] != 0.f);
+}
+
 int main(int argc, char** argv) {
     if (argc < 5) return 2;
+    devmem_owners();
     const char *dit = argv[1], *vae = argv[2], *text = argv[3], *gguf = argv[4];
     ace_ggml_context* ctx = nullptr;
     EXPECT(ace_ggml_create(nullptr, &ctx) == ACE_GGML_OK);

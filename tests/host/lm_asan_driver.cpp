@@ -80,6 +80,10 @@ int main(int argc, char** argv) {
         EXPECT(ace_mi_lm_forward(ctx, many.data(), nullptr, 258, logits.data(), nullptr) == ACE_GGML_OK);
         EXPECT(ace_mi_lm_forward(ctx, tok, nullptr, 1, logits.data(), nullptr) == ACE_GGML_OK);
         EXPECT(finite(std::vector<float>(logits.begin(), logits.begin() + 1000)));
+        EXPECT(ace_mi_lm_begin(ctx, 2, 7) == ACE_GGML_OK);  // back to a small cache inside the regrown buffers
+        EXPECT(ace_mi_lm_forward(ctx, ids.data(), mask.data(), 5, logits.data(), nullptr) == ACE_GGML_OK);
+        EXPECT(ace_mi_lm_forward(ctx, tok, one, 1, logits.data(), nullptr) == ACE_GGML_OK);
+        EXPECT(finite(logits));
     }
     ace_ggml_destroy(ctx);
     std::printf("%d failures\n", failures);
