@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = (
     "ace_ggml_text_encoder_forward_layers", "ace_ggml_generate_audio_simple", "ace_ggml_generate_audio_style_lyric_simple",
     "ace_ggml_generate_audio_style_lyric_timbre_simple", "ace_mi_reference_noise",
     "ace_mi_load_lm", "ace_mi_lm_get_info", "ace_mi_lm_begin", "ace_mi_lm_forward", "ace_mi_lm_reset",
-    "ace_mi_lm_select", "ace_mi_lm_generate",
+    "ace_mi_lm_select", "ace_mi_lm_generate", "ace_mi_lm_fanout", "ace_mi_lm_uniforms",
 )
 
 # Every symbol declared in include/acestep_mi355x_selftest.h: the TEST library (libacestep_mi355x_selftest.so = the
@@ -56,7 +56,7 @@ SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_ker
                     "ace_mi_kernel_attn_policy", "ace_mi_attn_plan", "ace_mi_attn_plan_block", "ace_mi_attn_plan_tiles",
                     "ace_mi_kernel_lm_skinny", "ace_mi_kernel_lm_embed", "ace_mi_kernel_lm_qkv_post",
                     "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention", "ace_mi_kernel_lm_skinny_q",
-                    "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_select",
+                    "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_select", "ace_mi_kernel_lm_cache_fanout",
                     "ace_mi_kernel_conv_gemm", "ace_mi_kernel_conv_out", "ace_mi_kernel_pack_f16",
                     "ace_mi_rope_table", "ace_mi_rope_table_steps")
 
@@ -282,6 +282,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.ace_mi_lm_select.restype = ctypes.c_int
         lib.ace_mi_lm_generate.argtypes = [vp, pp, vp, i32, vp, vp, vp, ip, vp]
         lib.ace_mi_lm_generate.restype = ctypes.c_int
+        lib.ace_mi_lm_fanout.argtypes = [vp, i32, i32, vp, vp]
+        lib.ace_mi_lm_fanout.restype = ctypes.c_int
+        lib.ace_mi_lm_uniforms.argtypes = [ctypes.c_uint64, i64, fp]
+        lib.ace_mi_lm_uniforms.restype = ctypes.c_int
     if path is None:
         _LIB = lib
     return lib
@@ -642,6 +646,35 @@ class GGMLCAPIBridge:
         self._ensure_ok(st, "ace_mi_lm_generate")
         del keep
         return out[:S], int(n_out.value)
+
+    def lm_fanout(self, copies: int, capacity: int, logits=None):
+        """Re-lay the live cache of G = 1 or 2 sequences for G * copies sequences of up to `capacity` positions
+        (ace_mi_lm_fanout): sequence g * copies + s is a bit copy of sequence g.  logits: the f32 [G, vocab] tensor of
+        the prefill, or None; returns the [G * copies, vocab] tensor whose row g * copies + s is row g (None without
+        logits).  Synchronous."""
+        import torch
+        from .hook import _OrderedCall
+        copies = int(copies)
+        if logits is None:
+            self._ensure_ok(self.lib.ace_mi_lm_fanout(self.ctx, copies, int(capacity), None, None), "ace_mi_lm_fanout")
+            return None
+        if logits.dtype != torch.float32 or not logits.is_contiguous() or logits.dim() != 2:
+            raise ValueError("lm_fanout: logits must be a contiguous f32 [G, vocab] tensor")
+        G = logits.shape[0]
+        out = torch.empty((G * max(copies, 1), logits.shape[1]), dtype=torch.float32, device=logits.device)
+        out[:G].copy_(logits)
+        with _OrderedCall(self, logits.device) as stream:
+            st = self.lib.ace_mi_lm_fanout(self.ctx, copies, int(capacity), out.data_ptr(), stream or None)
+        self._ensure_ok(st, "ace_mi_lm_fanout")
+        return out
+
+    def lm_uniforms(self, seed: int, n: int) -> np.ndarray:
+        """The engine's uniform stream for one sequence (ace_mi_lm_uniforms): n f32 values of `seed`, what lm_generate
+        draws with uniforms=None and S == 1."""
+        out = np.empty((int(n),), np.float32)
+        st = self.lib.ace_mi_lm_uniforms(int(seed) & (2 ** 64 - 1), int(n), _fptr(out))
+        self._ensure_ok(st, "ace_mi_lm_uniforms")
+        return out
 
     # reference GGMLCAPIBridge names (scripts/run_non_ggml_real_case.py:255-281)
     def text_forward_full(self, token_ids, hidden_dim: int) -> np.ndarray:
@@ -1127,7 +1160,9 @@ def _bind_lm_kernels(lib):
     lib.ace_mi_kernel_lm_skinny_q.argtypes = [i32] * 8 + [u16p, u8p, fp, u16p, ip]
     lib.ace_mi_kernel_lm_embed_q.argtypes = [i32] * 4 + [u8p, ip, fp]
     lib.ace_mi_kernel_lm_select.argtypes = [ctypes.POINTER(AceMiKernelLmSelectArgs)]
-    for name in ("skinny", "embed", "qkv_post", "prefill_kv", "attention", "skinny_q", "embed_q", "select"):
+    lib.ace_mi_kernel_lm_cache_fanout.argtypes = [i32] * 7 + [u16p, u16p, ip, u16p, u16p, ip]
+    for name in ("skinny", "embed", "qkv_post", "prefill_kv", "attention", "skinny_q", "embed_q", "select",
+                 "cache_fanout"):
         getattr(lib, "ace_mi_kernel_lm_" + name).restype = ctypes.c_int
     return lib
 
@@ -1212,6 +1247,25 @@ def kernel_lm_embed_q(blocks: np.ndarray, qtype: str, ids: np.ndarray, lib=None)
                                                        b.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _iptr(i),
                                                        _fptr(out)))
     return out
+
+
+def kernel_lm_cache_fanout(k_src: np.ndarray, v_src: np.ndarray, mask_src: np.ndarray, k_dst: np.ndarray,
+                           v_dst: np.ndarray, mask_dst: np.ndarray, n: int, lib=None):
+    """launch_lm_cache_fanout on host arrays: sources [layers][G][hkv][cap_src][128] uint16 with mask [G][cap_src] int32,
+    destinations [layers][G * S][hkv][cap_dst][128] with mask [G * S][cap_dst] (their contents before the launch are
+    uploaded).  Returns copies of all six arrays after the launch, in the order given."""
+    lib = _lm_lib(lib)
+    ks, vs, kd, vd = (np.array(a, dtype=np.uint16, order="C") for a in (k_src, v_src, k_dst, v_dst))
+    ms, md = (np.array(a, dtype=np.int32, order="C") for a in (mask_src, mask_dst))
+    layers, G, hkv, cap_src = ks.shape[:4]
+    GS, cap_dst = kd.shape[1], kd.shape[3]
+    if (vs.shape != ks.shape or vd.shape != kd.shape or ks.shape[4] != 128 or kd.shape[4] != 128 or GS % G or
+            kd.shape[0] != layers or kd.shape[2] != hkv or ms.shape != (G, cap_src) or md.shape != (GS, cap_dst)):
+        raise ValueError("kernel_lm_cache_fanout: inconsistent shapes")
+    st = lib.ace_mi_kernel_lm_cache_fanout(layers, G, GS // G, hkv, cap_src, cap_dst, int(n), _u16ptr(ks), _u16ptr(vs),
+                                           _iptr(ms), _u16ptr(kd), _u16ptr(vd), _iptr(md))
+    _lm_status("cache_fanout", st)
+    return ks, vs, ms, kd, vd, md
 
 
 def kernel_lm_qkv_post(qkv: np.ndarray, hq: int, hkv: int, pos: int, eps: float, q_norm, k_norm, rope_cos, rope_sin,

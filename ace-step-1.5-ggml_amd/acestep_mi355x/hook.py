@@ -423,12 +423,14 @@ class EngineCausalLM:
                                   "_generate_with_constrained_decoding and _generate_with_cfg_custom; "
                                   "transformers' generate() is not supported")
 
-    def __call__(self, input_ids=None, attention_mask=None, past_key_values=None, use_cache=True, **kw):
+    def __call__(self, input_ids=None, attention_mask=None, past_key_values=None, use_cache=True, capacity=None, **kw):
+        """capacity: positions to reserve for a new prefill (default: the prompt plus max_new_tokens); a caller that
+        fans the cache out afterwards (generate_codes_fanout) reserves the prompt alone."""
         if input_ids is None or input_ids.dim() != 2:
             raise ValueError("input_ids must be a [B, n] tensor")
         B, n = int(input_ids.shape[0]), int(input_ids.shape[1])
         if past_key_values is None:
-            cap = min(self.info["max_positions"], n + self.max_new_tokens)
+            cap = min(self.info["max_positions"], n + self.max_new_tokens if capacity is None else max(int(capacity), n))
             self.bridge.lm_begin(B, cap)
             self._serial += 1
             self._live = _LmCacheHandle(self._serial)
@@ -479,6 +481,31 @@ class EngineCausalLM:
         self._live.length += int(n_codes) - 1
         self._last_logits = None  # scratch of the loop now
         return tokens[:, :n]
+
+    def generate_codes_fanout(self, seeds, n_codes: int, allowed_ids, eos_id: int, prompt_ids=None, **kw):
+        """The audio-code phase of len(seeds) items that share the prompt in the live cache, in one engine loop: the
+        cache of the prefill (one row, or the conditional / unconditional pair) is fanned out bit for bit to one
+        sequence (pair) per item (bridge.lm_fanout), then generate_codes runs once with uniforms [n_codes, S] whose
+        column s is the engine's stream of seeds[s] (bridge.lm_uniforms), so item s gets the tokens a one-item
+        generate_codes(seed=seeds[s]) on the same prefill gets.  prompt_ids [1, n] (a repetition penalty): the ids every
+        item holds so far.  kw: generate_codes' cfg_scale, temperatures, top_k, top_p, repetition_penalty.  Handles
+        from before the call are stale.  Returns int32 [S, n_codes]."""
+        import torch
+        if self._live is None or getattr(self, "_last_logits", None) is None:
+            raise ValueError("generate_codes_fanout: no live cache; run the prompt through the model first")
+        S, n_codes = len(seeds), int(n_codes)
+        length = self._live.length
+        cap = min(self.info["max_positions"], length + n_codes)
+        logits = self.bridge.lm_fanout(S, cap, self._last_logits)
+        self._serial += 1
+        self._live = _LmCacheHandle(self._serial)
+        self._live.length = length
+        self._last_logits = logits
+        u = np.stack([np.asarray(self.bridge.lm_uniforms(seed, n_codes), np.float32) for seed in seeds], axis=1)
+        if prompt_ids is not None:
+            prompt_ids = prompt_ids[:1].repeat(S, 1)
+        return self.generate_codes(n_codes, allowed_ids, eos_id, prompt_ids=prompt_ids,
+                                   uniforms=torch.from_numpy(np.ascontiguousarray(u)), **kw)
 
 
 def _state_name(proc) -> str:
@@ -588,7 +615,90 @@ def _engine_loop(handler, ids, mask, max_new_tokens, temperature, cfg_scale, top
     return out
 
 
-def install_lm_backend(llm_handler: Any, bridge, max_new_tokens: int = 4096, device_codes: bool = False) -> None:
+LM_FANOUT_ROWS = 8  # the engine's rows per decode step (LM_MAX_BATCH): 4 items under CFG, otherwise 8
+
+
+def _run_pt_fanout(handler, prompts, temperature, cfg_scale, negative_prompt, top_k, top_p, repetition_penalty,
+                   use_constrained_decoding, constrained_decoding_debug, target_duration, generation_phase, caption,
+                   lyrics, cot_text, seeds):
+    """The handler's batch mode of `_run_pt` (acestep/llm_inference.py) for items that share one prompt: per group of
+    4 (CFG) or 8 items one prefill, one cache fan-out and one engine loop, then per item what `_run_pt_single` does
+    with its loop's output.  Item i gets the text the sequential path gives it: the same prefill, the engine stream of
+    the seed that path would draw (torch.manual_seed(seeds[i]) where given, then the torch.randint of _engine_loop),
+    and a decode step whose rows do not depend on the batch.  Returns None, before anything ran on the engine, when the
+    call is not one this path serves."""
+    import torch
+    model = handler.llm
+    if not isinstance(prompts, (list, tuple)) or len(prompts) < 2 or any(p != prompts[0] for p in prompts[1:]):
+        return None
+    if not isinstance(model, EngineCausalLM):
+        return None
+    cfg = float(cfg_scale) > 1.0
+    if not cfg and not use_constrained_decoding:
+        return None  # the reference calls transformers' generate() here
+
+    def processor():  # the settings _run_pt hands _run_pt_single for a batch item
+        return handler._setup_constrained_processor(
+            use_constrained_decoding=use_constrained_decoding, constrained_decoding_debug=constrained_decoding_debug,
+            target_duration=target_duration, user_metadata=None, stop_at_reasoning=False, skip_genres=True,
+            skip_caption=True, skip_language=True, generation_phase=generation_phase, is_batch=False)
+
+    if _codes_handoff(processor()) is None:
+        return None  # tokens come before the code phase (or there is none): the per-token path
+    tok = handler.llm_tokenizer
+    if target_duration is not None and target_duration > 0:
+        max_new_tokens = int(max(10, min(600, target_duration)) * 5) + 500
+    else:
+        max_new_tokens = getattr(getattr(model, "config", None), "max_new_tokens", 4096)
+    if hasattr(handler, "max_model_len"):
+        max_new_tokens = min(max_new_tokens, handler.max_model_len - 64)
+    texts = []
+    per_group = LM_FANOUT_ROWS // (2 if cfg else 1)
+    with handler._load_model_context():
+        if cfg:
+            uncond = handler._build_unconditional_prompt(caption=caption, lyrics=lyrics, cot_text=cot_text,
+                                                         negative_prompt=negative_prompt,
+                                                         generation_phase=generation_phase, is_batch=False)
+            side = tok.padding_side
+            tok.padding_side = "left"
+            enc = tok([prompts[0], uncond], return_tensors="pt", padding=True, truncation=True)
+            tok.padding_side = side
+        else:
+            enc = tok(prompts[0], return_tensors="pt", padding=False, truncation=True)
+        ids = enc["input_ids"].to(handler.device)
+        am = enc.get("attention_mask", None)
+        am = am.to(handler.device) if am is not None else torch.ones_like(ids)
+        for g0 in range(0, len(prompts), per_group):
+            items = range(g0, min(g0 + per_group, len(prompts)))
+            proc = processor()
+            allowed, eos_id, left = _codes_handoff(proc)
+            n = min(left, max_new_tokens)
+            item_seeds = []
+            for i in items:
+                if seeds and i < len(seeds):
+                    torch.manual_seed(seeds[i])
+                    if torch.cuda.is_available():
+                        torch.cuda.manual_seed_all(seeds[i])
+                item_seeds.append(int(torch.randint(0, 2 ** 62, (1,)).item()))
+            with torch.inference_mode():
+                model(input_ids=ids, attention_mask=am, past_key_values=None, use_cache=True, capacity=ids.shape[1])
+                toks = model.generate_codes_fanout(
+                    item_seeds, n, allowed, eos_id, prompt_ids=ids[:1], cfg_scale=float(cfg_scale) if cfg else 1.0,
+                    codes_temperature=getattr(proc, "codes_temperature", None), temperature=temperature, top_k=top_k,
+                    top_p=top_p, repetition_penalty=repetition_penalty)
+            toks = toks.to(device="cpu", dtype=ids.dtype)
+            proc.codes_count = int(getattr(proc, "codes_count", 0)) + n
+            if n == left and n < max_new_tokens:  # the forced EOS of the duration constraint
+                toks = torch.cat([toks, torch.full((toks.shape[0], 1), eos_id, dtype=toks.dtype)], dim=1)
+                st = getattr(proc, "state", None)
+                proc.state = type(st)["COMPLETED"] if hasattr(type(st), "__members__") else "COMPLETED"
+            for s in range(len(items)):
+                texts.append(tok.decode(toks[s], skip_special_tokens=False))
+    return texts
+
+
+def install_lm_backend(llm_handler: Any, bridge, max_new_tokens: int = 4096, device_codes: bool = False,
+                       batch_codes: bool = False) -> None:
     """Point the reference LLM handler's `pt` backend at the engine: `llm_handler.llm` becomes an EngineCausalLM over
     the LM that `bridge.load_lm` loaded (needs no `transformers`).
 
@@ -599,7 +709,16 @@ def install_lm_backend(llm_handler: Any, bridge, max_new_tokens: int = 4096, dev
     non_audio_code_mask; everything left then runs in one generate_codes call, codes_count and the COMPLETED state are
     written back and EOS is appended.  A streamer, a processor that is disabled or has no target or mask, no
     processor, or a cfg_scale <= 1 in the CFG loop keep the per-token path.  Off by default: the engine draws from its own seeded uniforms, not torch.multinomial, so the same
-    torch seed gives other (equally distributed) codes."""
+    torch seed gives other (equally distributed) codes.
+
+    batch_codes=True (only together with device_codes=True, else ValueError) also replaces the handler's `_run_pt`
+    (same signature and return value): a list of at least 2 equal prompts, whose constrained processor is in
+    CODES_GENERATION with target_codes, eos_token_id and a mask right after its set-up (so no token is sampled before the
+    code phase), runs in groups of 4 items under CFG (cfg_scale > 1), otherwise 8: one prefill, one cache fan-out and one
+    generate_codes call per group (_run_pt_fanout), each item with the engine stream the sequential path would give
+    it, so the returned texts are the sequential path's.  Anything else runs the handler's own sequential `_run_pt`."""
+    if batch_codes and not device_codes:
+        raise ValueError("install_lm_backend: batch_codes=True needs device_codes=True")
     device = getattr(llm_handler, "device", None)
     if device is None or str(device) in ("auto", "cpu"):
         device = "cuda"
@@ -620,6 +739,26 @@ def install_lm_backend(llm_handler: Any, bridge, max_new_tokens: int = 4096, dev
         llm_handler._generate_with_constrained_decoding = types.MethodType(constrained_mi355x, llm_handler)
         llm_handler._generate_with_cfg_custom = types.MethodType(cfg_mi355x, llm_handler)
         setattr(llm_handler, "_ggml_lm_device_codes", True)
+    if batch_codes:
+        sequential = llm_handler._run_pt
+
+        def run_pt_mi355x(self, formatted_prompts, temperature, cfg_scale, negative_prompt, top_k, top_p,
+                          repetition_penalty, use_constrained_decoding=True, constrained_decoding_debug=False,
+                          target_duration=None, user_metadata=None, stop_at_reasoning=False, skip_genres=True,
+                          skip_caption=False, skip_language=False, generation_phase="cot", caption="", lyrics="",
+                          cot_text="", seeds=None):
+            out = _run_pt_fanout(self, formatted_prompts, temperature, cfg_scale, negative_prompt, top_k, top_p,
+                                 repetition_penalty, use_constrained_decoding, constrained_decoding_debug,
+                                 target_duration, generation_phase, caption, lyrics, cot_text, seeds)
+            if out is not None:
+                return out
+            return sequential(formatted_prompts, temperature, cfg_scale, negative_prompt, top_k, top_p,
+                              repetition_penalty, use_constrained_decoding, constrained_decoding_debug, target_duration,
+                              user_metadata, stop_at_reasoning, skip_genres, skip_caption, skip_language,
+                              generation_phase, caption, lyrics, cot_text, seeds)
+
+        llm_handler._run_pt = types.MethodType(run_pt_mi355x, llm_handler)
+        setattr(llm_handler, "_ggml_lm_batch_codes", True)
 
 
 def install_text_encoder_backend(dit_handler: Any, bridge) -> None:

@@ -474,6 +474,33 @@ size_t lm_attn_part_floats(int B, int hq, int nk);
 // >= nk are not read, and a sequence whose keys are all masked gets exactly +0 in every output word of either type.
 void launch_lm_attention(ActType out_t, const LmAttnArgs& a, int B, int hq, hipStream_t s);
 
+// ------------------------------------------------------------ LM cache fan-out (kernels/lm_fanout.hip)
+// A prefilled cache of G = 1 or 2 sequences re-laid for G * S sequences: destination sequence g * S + s is a bit copy of
+// source sequence g over positions [0, n); positions [n, cap_dst) of the destination are not written.  Source K and V
+// [layers][G][hkv][cap_src][128] fp16 with key mask [G][cap_src]; destination [layers][G * S][hkv][cap_dst][128] with
+// [G * S][cap_dst].  The two caches must be different allocations.
+struct LmFanoutArgs {
+    const uint16_t* k_src = nullptr;
+    const uint16_t* v_src = nullptr;
+    const int32_t* mask_src = nullptr;
+    uint16_t* k_dst = nullptr;
+    uint16_t* v_dst = nullptr;
+    int32_t* mask_dst = nullptr;
+    int layers = 0, G = 0, S = 0, hkv = 0;
+    int cap_src = 0, cap_dst = 0;
+    int n = 0;  // positions held by the source
+};
+inline void lm_fanout_check(const LmFanoutArgs& a) {
+    ACEMI_CHECK(a.k_src && a.v_src && a.mask_src && a.k_dst && a.v_dst && a.mask_dst && a.k_src != a.k_dst &&
+                    a.v_src != a.v_dst && a.mask_src != a.mask_dst,
+                "lm_cache_fanout: null or aliased buffers");
+    ACEMI_CHECK((a.G == 1 || a.G == 2) && a.S >= 1 && a.G * a.S <= LM_MAX_BATCH && a.layers >= 1 && a.hkv >= 1 &&
+                    (int64_t)a.layers * a.hkv <= 65535,
+                "lm_cache_fanout: bad batch or layer shape");
+    ACEMI_CHECK(a.n >= 1 && a.n <= a.cap_src && a.n <= a.cap_dst, "lm_cache_fanout: positions outside a cache");
+}
+void launch_lm_cache_fanout(const LmFanoutArgs& a, hipStream_t s);
+
 // ------------------------------------------------------------ LM token selection (kernels/lm_sample.hip)
 // One token per sampled sequence from the f32 logits of a forward: CFG mix, candidate set, phase temperature,
 // repetition penalty, top-k, top-p, then a draw (or the argmax) -- the codes-phase pipeline of the reference's loops.

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../kernels/lm_decode_q_host.h"  // empty under hipcc; the host build's launch_lm_skinny_q / launch_lm_embed_q
+#include "../kernels/lm_fanout_host.h"    // empty under hipcc; the host build's launch_lm_cache_fanout
 #include "../kernels/lm_sample_host.h"    // empty under hipcc; the host build's launch_lm_select
 #include "context.h"
 #include "safetensors.h"
@@ -27,6 +28,12 @@ namespace acemi {
 
 // tokens between two host reads of the loop's stop word (ace_mi_lm_generate)
 constexpr int LM_STOP_POLL = 16;
+
+// the uniform stream of ace_mi_lm_generate / ace_mi_lm_uniforms: std::mt19937_64(seed), (x >> 40) * 2^-24 per output
+inline void lm_uniform_stream(uint64_t seed, size_t n, float* out) {
+    std::mt19937_64 gen(seed);
+    for (size_t i = 0; i < n; ++i) out[i] = (float)(gen() >> 40) * (1.0f / 16777216.0f);
+}
 
 class LmEngine {
    public:
@@ -76,6 +83,49 @@ class LmEngine {
         batch_ = B;
         capacity_ = cap;
         len_ = 0;
+    }
+
+    // The cache of batch_ = G sequences re-laid for G * copies sequences of `cap` positions (kernels/lm_fanout.hip):
+    // sequence g * copies + s is a bit copy of sequence g, the logits rows follow, len_ stays.  The caller has checked
+    // the arguments.  The new cache is allocated beside the old one, which is released once the copy has finished on
+    // `s`; a throw before that leaves the engine as it was.
+    void fanout(int copies, int cap, float* d_logits, hipStream_t s) {
+        const TextConfig& c = model_.cfg;
+        const int G = batch_, B = G * copies;
+        if (copies == 1 && cap == capacity_) return;
+        const size_t plane = (size_t)c.layers * B * c.hkv * cap * c.head_dim * 2;
+        DevBuf kn, vn, mn;
+        kn.ensure(plane);
+        vn.ensure(plane);
+        mn.ensure((size_t)B * cap * 4);
+        rope_.ensure(cap, c.head_dim, c.rope_theta, s);
+        part_.ensure(lm_attn_part_floats(B, c.hq, cap) * 4);
+        LmFanoutArgs a;
+        a.k_src = kc_.as<uint16_t>();
+        a.v_src = vc_.as<uint16_t>();
+        a.mask_src = kmask_.as<int32_t>();
+        a.k_dst = kn.as<uint16_t>();
+        a.v_dst = vn.as<uint16_t>();
+        a.mask_dst = mn.as<int32_t>();
+        a.layers = c.layers;
+        a.G = G;
+        a.S = copies;
+        a.hkv = c.hkv;
+        a.cap_src = capacity_;
+        a.cap_dst = cap;
+        a.n = len_;
+        launch_lm_cache_fanout(a, s);
+        if (d_logits)  // descending: row r is read only by rows >= r, all written before it is overwritten
+            for (int r = B - 1; r > 0; --r)
+                if (r / copies != r)
+                    ACEMI_HIP(hipMemcpyAsync(d_logits + (size_t)r * c.vocab, d_logits + (size_t)(r / copies) * c.vocab,
+                                             (size_t)c.vocab * 4, hipMemcpyDeviceToDevice, s));
+        ACEMI_HIP(hipStreamSynchronize(s));  // the copy has read the old cache: it may go
+        kc_ = std::move(kn);
+        vc_ = std::move(vn);
+        kmask_ = std::move(mn);
+        batch_ = B;
+        capacity_ = cap;
     }
 
     // the caller has checked batch, capacity and the prefill rule
@@ -143,8 +193,7 @@ class LmEngine {
         sel_done_.ensure((size_t)(1 + LM_MAX_BATCH) * 4);
         if (!d_uniform && p.temperature > 0.0f) {
             std::vector<float> u((size_t)n_max * a.S);
-            std::mt19937_64 gen(p.seed);
-            for (float& v : u) v = (float)(gen() >> 40) * (1.0f / 16777216.0f);
+            lm_uniform_stream(p.seed, u.size(), u.data());
             sel_uni_.ensure(u.size() * 4);
             ACEMI_HIP(hipDeviceSynchronize());  // an earlier loop, on any stream, may still read the buffer
             ACEMI_HIP(hipMemcpy(sel_uni_.p, u.data(), u.size() * 4, hipMemcpyHostToDevice));
@@ -494,6 +543,34 @@ ace_ggml_status ace_mi_lm_generate(ace_ggml_context* ctx, const ace_mi_lm_sample
     } catch (const std::exception& ex) {
         return set_error(ctx, ACE_GGML_ERR, std::string("lm generate failed: ") + ex.what());
     }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_lm_fanout(ace_ggml_context* ctx, int32_t copies, int32_t capacity, float* d_logits, void* stream) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->lm) return set_error(ctx, ACE_GGML_ERR, "lm not loaded");
+    acemi::LmEngine* e = lm_of(ctx);
+    if (copies < 1) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm fanout: copies < 1");
+    if (e->batch() < 1 || e->batch() > 2)
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm fanout: the cache must hold 1 or 2 sequences");
+    if ((int64_t)e->batch() * copies > acemi::LM_MAX_BATCH)
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm fanout: more than 8 sequences");
+    if (e->len() < 1) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm fanout: the cache is empty");
+    if (capacity < e->len() || capacity > e->model().cfg.max_pos)
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm fanout: capacity must be cache_len..max_position_embeddings");
+    try {
+        bind_device(ctx);
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+        e->fanout(copies, capacity, d_logits, s);
+    } catch (const std::exception& ex) {
+        return set_error(ctx, ACE_GGML_ERR, std::string("lm fanout failed: ") + ex.what());
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_lm_uniforms(uint64_t seed, int64_t n, float* out) {
+    if (n < 0 || (n > 0 && !out)) return ACE_GGML_ERR_INVALID_ARG;
+    acemi::lm_uniform_stream(seed, (size_t)n, out);
     return ACE_GGML_OK;
 }
 

@@ -295,6 +295,46 @@ ace_ggml_status ace_mi_kernel_lm_select(const ace_mi_kernel_lm_select_args* g) {
     return ACE_GGML_OK;
 }
 
+ace_ggml_status ace_mi_kernel_lm_cache_fanout(int32_t layers, int32_t G, int32_t S, int32_t hkv, int32_t cap_src,
+                                              int32_t cap_dst, int32_t n, uint16_t* k_src, uint16_t* v_src,
+                                              int32_t* mask_src, uint16_t* k_dst, uint16_t* v_dst, int32_t* mask_dst) {
+    using namespace acemi;
+    if ((G != 1 && G != 2) || S < 1 || G * S > LM_MAX_BATCH || layers < 1 || hkv < 1 || (int64_t)layers * hkv > 65535 ||
+        n < 1 || n > cap_src || n > cap_dst || !k_src || !v_src || !mask_src || !k_dst || !v_dst || !mask_dst)
+        return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const size_t ns = (size_t)layers * G * hkv * cap_src * D * 2, ms = (size_t)G * cap_src * 4;
+        const size_t nd = (size_t)layers * G * S * hkv * cap_dst * D * 2, md = (size_t)G * S * cap_dst * 4;
+        DevMem dks(k_src, ns), dvs(v_src, ns), dms(mask_src, ms), dkd(k_dst, nd), dvd(v_dst, nd), dmd(mask_dst, md);
+        LmFanoutArgs a;
+        a.k_src = dks.as<uint16_t>();
+        a.v_src = dvs.as<uint16_t>();
+        a.mask_src = dms.as<int32_t>();
+        a.k_dst = dkd.as<uint16_t>();
+        a.v_dst = dvd.as<uint16_t>();
+        a.mask_dst = dmd.as<int32_t>();
+        a.layers = layers;
+        a.G = G;
+        a.S = S;
+        a.hkv = hkv;
+        a.cap_src = cap_src;
+        a.cap_dst = cap_dst;
+        a.n = n;
+        launch_lm_cache_fanout(a, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dks.to_host(k_src, ns);
+        dvs.to_host(v_src, ns);
+        dms.to_host(mask_src, ms);
+        dkd.to_host(k_dst, nd);
+        dvd.to_host(v_dst, nd);
+        dmd.to_host(mask_dst, md);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_cache_fanout: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
 ace_ggml_status ace_mi_kernel_lm_attention(int32_t out_type, int32_t B, int32_t hq, int32_t hkv, int32_t capacity,
                                            int32_t nk, float scale, const float* q, const uint16_t* k_cache,
                                            const uint16_t* v_cache, const int32_t* key_mask, uint16_t* out_u16) {

@@ -333,6 +333,32 @@ ACE_GGML_API ace_ggml_status ace_mi_lm_generate(ace_ggml_context* ctx, const ace
                                                 float* d_logits, int32_t n_max, const float* d_uniform,
                                                 uint8_t* d_seen, int32_t* d_tokens, int32_t* n_out, void* stream);
 
+/* ---- one decode loop for the items of a request that share a prompt (kernels/lm_fanout.hip).  Item s of the batched
+ * loop gets, token for token, what a one-item run with the same uniforms gets: the prompt is prefilled once, exactly as
+ * the one-item run prefills it (a prefill of more rows may pick other GEMM tiles and sum in another order), its cache
+ * rows are copied bit for bit, and every kernel of the decode step treats a row independently of the batch.
+ * Recommended call order, which keeps the peak at one small source cache plus the destination cache:
+ *   1. ace_mi_lm_begin(G, n_prompt)                    G = 2 under CFG (conditional, unconditional), else 1
+ *   2. ace_mi_lm_forward with the prompt
+ *   3. ace_mi_lm_fanout(S, n_prompt + n_max, d_logits)
+ *   4. ace_mi_lm_generate with d_uniform [n_max][S], column s = ace_mi_lm_uniforms(seed of item s, n_max)
+ * Meant for the duration-constrained case (min_tokens == n_max, nothing polled), where every item emits the same
+ * number of codes; ace_mi_lm_generate, ace_mi_lm_select and their stop semantics are unchanged. ---- */
+/* After the prompt is in the cache of a batch of G = 1 or 2 sequences: re-lay the cache for G*copies sequences of up to
+ * `capacity` positions; sequence g*copies + s is a bit copy of sequence g (K, V, key mask, cache_len).  d_logits, when
+ * not NULL, holds [G][vocab] on entry and [G*copies][vocab] on return (row g*copies + s = row g).  Synchronous, like
+ * ace_mi_lm_begin.  copies == 1 with capacity == the current one changes nothing.  The new cache is allocated beside
+ * the old one, which is released once the copy has finished.
+ * ACE_GGML_ERR_INVALID_ARG, with cache, batch, capacity and cache_len unchanged: copies < 1, G > 2 (or no
+ * ace_mi_lm_begin), G*copies > 8, an empty cache, capacity < cache_len, capacity > max_positions.  ACE_GGML_ERR "lm
+ * not loaded" before ace_mi_load_lm. */
+ACE_GGML_API ace_ggml_status ace_mi_lm_fanout(ace_ggml_context* ctx, int32_t copies, int32_t capacity, float* d_logits,
+                                              void* stream);
+/* The engine's uniform stream, as ace_mi_lm_generate draws it with d_uniform == NULL and one sequence: n values of
+ * std::mt19937_64(seed), (x >> 40) * 2^-24, into out (host).  Lets a caller give every item of a batch its own stream
+ * through d_uniform [n_max][S], whatever the grouping. */
+ACE_GGML_API ace_ggml_status ace_mi_lm_uniforms(uint64_t seed, int64_t n, float* out);
+
 /* The x_T stream of the reference generator (std::mt19937(seed) + std::normal_distribution<float>,
  * acestep_ggml.cpp:2043-2048) as the generate entries draw it: n values into out (host). */
 ACE_GGML_API ace_ggml_status ace_mi_reference_noise(int32_t seed, int64_t n, float* out);

@@ -204,6 +204,16 @@ typedef struct ace_mi_kernel_lm_select_args {
     int32_t* chains;
 } ace_mi_kernel_lm_select_args;
 ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_select(const ace_mi_kernel_lm_select_args* args);
+/* Cache fan-out (kernels/lm_fanout.hip through launch_lm_cache_fanout) on host arrays: source k_src / v_src
+ * [layers][G][hkv][cap_src][128] fp16 words and mask_src [G][cap_src]; destination k_dst / v_dst
+ * [layers][G * S][hkv][cap_dst][128] and mask_dst [G * S][cap_dst].  Every array is in-out: uploaded, the launch copies
+ * positions [0, n) of source sequence g to destination sequence g * S + s, and all six are read back (a source the
+ * launch wrote to, or a destination word past n it touched, shows).  ACE_GGML_ERR_INVALID_ARG for what the launcher
+ * refuses: G not 1 or 2, S < 1, G * S > 8, n < 1 or past either capacity. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_cache_fanout(int32_t layers, int32_t G, int32_t S, int32_t hkv,
+                                                           int32_t cap_src, int32_t cap_dst, int32_t n, uint16_t* k_src,
+                                                           uint16_t* v_src, int32_t* mask_src, uint16_t* k_dst,
+                                                           uint16_t* v_dst, int32_t* mask_dst);
 /* ---- VAE conv kernels (csrc/kernels/vae.hip through launch_conv_gemm / launch_conv_out / launch_pack_f16 /
  * launch_to_f16 of csrc/kernels.h).  One launch each on host buffers, on a stream, blocking.
  * conv_gemm: the integer fields are those of ConvGemmArgs.  S [items][T_in][Cin] and W [N][taps * Cin] fp16 words;
