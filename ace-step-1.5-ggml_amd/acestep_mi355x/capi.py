@@ -50,7 +50,7 @@ EXPORTED_SYMBOLS = (
 # product objects + the kernel self-test / micro-benchmark entries); the product library does not export them.
 SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_kernel_attn_probs", "ace_mi_bench_attention", "ace_mi_bench_gemm",
                     "ace_mi_kernel_gemm_q", "ace_mi_kernel_dequant", "ace_mi_bench_gemm_q", "ace_mi_kernel_gemm_a8",
-                    "ace_mi_kernel_gemm_a8_mode", "ace_mi_kernel_attn_kh", "ace_mi_kernel_lora_merge",
+                    "ace_mi_kernel_gemm_a8_mode", "ace_mi_kernel_attn_kh", "ace_mi_kernel_lora_merge", "ace_mi_kernel_lokr_merge",
                     "ace_mi_kernel_dequant_blocks", "ace_mi_kernel_dequant_segments", "ace_mi_bench_dequant_blocks",
                     "ace_mi_gemm_resolve", "ace_mi_gemm_variant_row", "ace_mi_gemm_variant_arg_ok",
                     "ace_mi_kernel_attn_policy", "ace_mi_attn_plan", "ace_mi_attn_plan_block", "ace_mi_attn_plan_tiles",
@@ -142,6 +142,12 @@ class AceMiLoraJob(ctypes.Structure):
                 ("A", ctypes.POINTER(ctypes.c_float)), ("B", ctypes.POINTER(ctypes.c_float)), ("eff", ctypes.c_float),
                 ("map", ctypes.c_int32), ("row_off", ctypes.c_int32), ("half", ctypes.c_int32),
                 ("copy_rest", ctypes.c_int32)]
+
+
+class AceMiLokrJob(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("row0", "rows", "a", "b", "c", "d", "r1", "r2")] + [
+        (n, ctypes.POINTER(ctypes.c_float)) for n in ("w1", "w1a", "w1b", "w2", "w2a", "w2b")] + [
+        ("eff", ctypes.c_float)] + [(n, ctypes.c_int32) for n in ("map", "row_off", "half", "copy_rest")]
 
 
 _LIB = None
@@ -373,6 +379,8 @@ def load_selftest_library() -> ctypes.CDLL:
     lib.ace_mi_kernel_attn_kh.restype = ctypes.c_int
     lib.ace_mi_kernel_lora_merge.argtypes = [i32, i32, i32, i32, i32, u16p, u16p, ctypes.POINTER(AceMiLoraJob), i32]
     lib.ace_mi_kernel_lora_merge.restype = ctypes.c_int
+    lib.ace_mi_kernel_lokr_merge.argtypes = [i32, i32, i32, i32, i32, u16p, u16p, ctypes.POINTER(AceMiLokrJob), i32]
+    lib.ace_mi_kernel_lokr_merge.restype = ctypes.c_int
     _bind_dequant_blocks(lib)
     lib.ace_mi_bench_dequant_blocks.argtypes = [i32, i32, i32, i32, i32, fp]
     lib.ace_mi_bench_dequant_blocks.restype = ctypes.c_int
@@ -854,8 +862,9 @@ class GGMLCAPIBridge:
 
     # -- PEFT LoRA adapters (include/acestep_mi355x.h) -----------------------------------------------
     def load_lora(self, path, scale: float = 1.0) -> None:
-        """Load adapter_config.json + adapter_model.safetensors of `path` at strength `scale` (replaces any
-        previous adapter; synchronous)."""
+        """Load adapter_config.json + adapter_model.safetensors of `path` (PEFT LoRA), or lokr_weights.safetensors
+        (LyCORIS LoKr: `path` is that file, or a directory that holds it and no adapter_config.json), at strength
+        `scale` (replaces any previous adapter; synchronous)."""
         st = self.lib.ace_mi_dit_load_lora(self.ctx, str(path).encode("utf-8"), float(scale))
         self._ensure_ok(st, "ace_mi_dit_load_lora")
 
@@ -1142,6 +1151,45 @@ def kernel_lora_merge(base_bits: Optional[np.ndarray], out_bits: np.ndarray, col
                                       arr, len(jobs))
     if st != ACE_GGML_OK:
         raise RuntimeError(f"ace_mi_kernel_lora_merge failed (status={st})")
+    return out
+
+
+def kernel_lokr_merge(base_bits: Optional[np.ndarray], out_bits: np.ndarray, cols: int, jobs, fmt: str = "bf16",
+                      lib=None) -> np.ndarray:
+    """launch_lokr_merge on host arrays, as kernel_lora_merge: each job a dict (row0, rows, eff, map, row_off, half,
+    copy_rest) with the Kronecker factors w1 = an [a][b] f32 array or a pair ([a][r], [r][b]), w2 = [c][d] or
+    ([c][r], [r][d]); no w1: a copy-only job."""
+    lib = lib or load_selftest_library()
+    out = np.array(out_bits, dtype=np.uint16, order="C", copy=True)
+    base = None if base_bits is None else np.ascontiguousarray(base_bits, dtype=np.uint16)
+    keep = []
+
+    def factor(f):
+        """(rows, cols, rank, whole, left, right) of a factor given whole or as a pair."""
+        if isinstance(f, tuple):
+            l, r = (np.ascontiguousarray(x, dtype=np.float32) for x in f)
+            keep.extend((l, r))
+            return l.shape[0], r.shape[1], l.shape[1], None, _fptr(l), _fptr(r)
+        f = np.ascontiguousarray(f, dtype=np.float32)
+        keep.append(f)
+        return f.shape[0], f.shape[1], 0, _fptr(f), None, None
+
+    arr = (AceMiLokrJob * len(jobs))()
+    for i, j in enumerate(jobs):
+        kw = dict(row0=int(j["row0"]), rows=int(j["rows"]), eff=float(j.get("eff", 0.0)), map=int(j.get("map", 0)),
+                  row_off=int(j.get("row_off", 0)), half=int(j.get("half", 0)), copy_rest=1 if j.get("copy_rest") else 0)
+        if j.get("w1") is not None:
+            a, b, r1, w1, w1a, w1b = factor(j["w1"])
+            c, d, r2, w2, w2a, w2b = factor(j["w2"])
+            kw.update(a=a, b=b, c=c, d=d, r1=r1, r2=r2, w1=w1, w1a=w1a, w1b=w1b, w2=w2, w2a=w2a, w2b=w2b)
+        arr[i] = AceMiLokrJob(**kw)
+    u16p = ctypes.POINTER(ctypes.c_uint16)
+    st = lib.ace_mi_kernel_lokr_merge({"bf16": 0, "fp16": 1}[fmt], out.shape[0], int(cols),
+                                      0 if base is None else base.shape[1], out.shape[1],
+                                      None if base is None else base.ctypes.data_as(u16p), out.ctypes.data_as(u16p),
+                                      arr, len(jobs))
+    if st != ACE_GGML_OK:
+        raise RuntimeError(f"ace_mi_kernel_lokr_merge failed (status={st})")
     return out
 
 

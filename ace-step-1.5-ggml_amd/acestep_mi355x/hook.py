@@ -207,7 +207,10 @@ def install_lora_backend(dit_handler: Any, bridge) -> None:
         lora_path = str(lora_path).strip()
         if not os.path.exists(lora_path):
             return f"❌ LoRA path not found: {lora_path}"
-        if not os.path.exists(os.path.join(lora_path, "adapter_config.json")):
+        # a PEFT LoRA directory, or a LyCORIS LoKr one (lokr_weights.safetensors, or that file itself)
+        lokr = os.path.basename(lora_path) == "lokr_weights.safetensors" or \
+            os.path.exists(os.path.join(lora_path, "lokr_weights.safetensors"))
+        if not lokr and not os.path.exists(os.path.join(lora_path, "adapter_config.json")):
             return f"❌ Invalid LoRA adapter: adapter_config.json not found in {lora_path}"
         try:
             bridge.load_lora(lora_path, float(self.lora_scale))

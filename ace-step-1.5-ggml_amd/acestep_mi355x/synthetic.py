@@ -726,6 +726,12 @@ def merged_checkpoint(base_dir: str, adapter_dir: str, scale: float, out_dir: st
         eff = lora_eff(scale, alpha, A.shape[0], bool(conf.get("use_rslora")))
         merged = lora_merge_bits(words.reshape(shape), lora_acc(A, B), eff, dt)
         tensors[key] = (dt, shape, merged.reshape(-1))
+    _write_safetensors_raw(os.path.join(out_dir, "model.safetensors"), tensors)
+    return out_dir
+
+
+def _write_safetensors_raw(path: str, tensors) -> None:
+    """{name: (dtype, shape, raw words / f32 array)} as _read_safetensors_raw returns it."""
     header: Dict[str, dict] = {}
     off = 0
     for name, (dt, shape, words) in tensors.items():
@@ -733,11 +739,148 @@ def merged_checkpoint(base_dir: str, adapter_dir: str, scale: float, out_dir: st
         off += words.nbytes
     hjson = json.dumps(header, separators=(",", ":")).encode("utf-8")
     hjson += b" " * ((8 - len(hjson) % 8) % 8)
-    tmp = os.path.join(out_dir, "model.safetensors.tmp")
-    with open(tmp, "wb") as f:
+    with open(path + ".tmp", "wb") as f:
         f.write(struct.pack("<Q", len(hjson)))
         f.write(hjson)
         for _, (_, _, words) in tensors.items():
             f.write(words.tobytes())
-    os.replace(tmp, os.path.join(out_dir, "model.safetensors"))
+    os.replace(path + ".tmp", path)
+
+
+# ----------------------------------------------------------------------------- LyCORIS LoKr adapters
+# What the reference trainer saves (acestep/training/lokr_utils.py:184-204, configs.py:42-75): one file
+# lokr_weights.safetensors, header metadata algo = lokr, format = lycoris and lokr_config = the config's JSON, tensors
+# lycoris_<module path with _ for .>.{lokr_w1 | lokr_w1_a, lokr_w1_b}, .{lokr_w2 | lokr_w2_a, lokr_w2_b}, .alpha.
+# The delta of a module is kron(w1 [a][b], w2 [c][d]) * unit, unit = 1 with both factors whole, else alpha / r
+# (alpha / sqrt(r) with rs_lora).  The names and the scale rule are LyCORIS's as documented; this writer has not been
+# pinned against a file the library itself wrote.
+LOKR_FORMS = ("full", "w2_lowrank", "both_lowrank")
+
+
+def lokr_factorization(dim: int, factor: int = -1) -> Tuple[int, int]:
+    """(m, n), m <= n, m * n = dim: `factor` and its cofactor when it divides dim, else the most balanced pair whose
+    smaller side does not exceed `factor` (-1: no limit), as LyCORIS splits a dimension."""
+    if factor > 0 and dim % factor == 0:
+        return tuple(sorted((factor, dim // factor)))
+    limit = dim if factor < 0 else factor
+    m = max(k for k in range(1, int(np.sqrt(dim)) + 1) if dim % k == 0 and k <= limit)
+    return m, dim // m
+
+
+def lokr_name(module: str) -> str:
+    """"layers.0.self_attn.q_proj" -> "lycoris_layers_0_self_attn_q_proj"."""
+    return "lycoris_" + module.replace(".", "_")
+
+
+def write_lokr_adapter(out_dir: str, cfg: dict, r: int = 4, alpha: float = 8.0, factor: int = -1,
+                       form: str = "w2_lowrank", targets=LORA_ATTN_TARGETS, seed: int = 0, dtype: str = "F32",
+                       rs_lora: bool = False, scalar: Optional[float] = None, std: float = 0.05,
+                       config: bool = True, extra_config=None) -> str:
+    """Write lokr_weights.safetensors by hand, every factor ~ N(0, std) (LyCORIS initialises w2 to zero; a non-zero
+    w2 makes the delta visible).  form: which factors are stored as low-rank pairs (LOKR_FORMS).  config: write the
+    lokr_config metadata (the checkpoint path of the trainer writes it, the final save does not)."""
+    assert form in LOKR_FORMS, form
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(seed)
+    f = lambda *sh: rng.standard_normal(sh, dtype=np.float32) * np.float32(std)
+    tensors = []
+    for i in range(cfg["num_hidden_layers"]):
+        for m in _expand_targets(targets):
+            fin, fout = lora_module_dims(cfg, m)
+            (a, c), (b, d) = lokr_factorization(fout, factor), lokr_factorization(fin, factor)
+            name = lokr_name(f"layers.{i}.{m}")
+            if form == "both_lowrank":
+                tensors += [(f"{name}.lokr_w1_a", f(a, r)), (f"{name}.lokr_w1_b", f(r, b))]
+            else:
+                tensors.append((f"{name}.lokr_w1", f(a, b)))
+            if form == "full":
+                tensors.append((f"{name}.lokr_w2", f(c, d)))
+            else:
+                tensors += [(f"{name}.lokr_w2_a", f(c, r)), (f"{name}.lokr_w2_b", f(r, d))]
+            tensors.append((f"{name}.alpha", np.asarray(r if form == "full" else alpha, np.float32)))
+            if scalar is not None:
+                tensors.append((f"{name}.scalar", np.asarray(scalar, np.float32)))
+    meta = {"algo": "lokr", "format": "lycoris"}
+    if config:
+        conf = dict(linear_dim=r, linear_alpha=alpha, factor=factor, decompose_both=form == "both_lowrank",
+                    use_tucker=False, use_scalar=scalar is not None, weight_decompose=False,
+                    target_modules=sorted({m.split(".")[-1] for m in _expand_targets(targets)}),
+                    full_matrix=form == "full", bypass_mode=False, rs_lora=bool(rs_lora),
+                    unbalanced_factorization=False)
+        conf.update(extra_config or {})
+        meta["lokr_config"] = json.dumps(conf, ensure_ascii=True)
+    path = os.path.join(out_dir, "lokr_weights.safetensors")
+    write_safetensors(path, tensors, dtype)
+    set_safetensors_metadata(path, meta)
+    return out_dir
+
+
+def set_safetensors_metadata(path: str, meta: Dict[str, str]) -> None:
+    """Rewrite the header of a safetensors file with __metadata__ = meta (the data is kept as it is)."""
+    with open(path, "rb") as f:
+        n = struct.unpack("<Q", f.read(8))[0]
+        header = json.loads(f.read(n))
+        data = f.read()
+    header["__metadata__"] = dict(meta)
+    hjson = json.dumps(header, separators=(",", ":")).encode("utf-8")
+    hjson += b" " * ((8 - len(hjson) % 8) % 8)
+    with open(path + ".tmp", "wb") as f:
+        f.write(struct.pack("<Q", len(hjson)) + hjson + data)
+    os.replace(path + ".tmp", path)
+
+
+def lokr_delta(w1, w2) -> np.ndarray:
+    """The merge kernels' delta before the scale, float32 [a*c][b*d]: each factor whole or a pair (L, R) formed by the
+    rank-ascending chain of lora_acc, then one rounded multiply w1[i][j] * w2[k][l]."""
+    w1, w2 = (lora_acc(f[1], f[0]) if isinstance(f, tuple) else np.ascontiguousarray(f, np.float32) for f in (w1, w2))
+    (a, b), (c, d) = w1.shape, w2.shape
+    return (w1[:, None, :, None] * w2[None, :, None, :]).reshape(a * c, b * d)
+
+
+def lokr_eff(scale: float, alpha, r: int, rs_lora: bool = False, scalar=1.0) -> np.float32:
+    """f32(scale) * (unit * f32(scalar)), unit = 1 (r = 0: both factors whole) or f32(alpha / r) (alpha / sqrt(r)
+    with rs_lora), the engine's per-module scale."""
+    alpha = float(np.float32(alpha))
+    unit = np.float32(1.0) if r == 0 else np.float32(alpha / np.sqrt(float(r)) if rs_lora else alpha / float(r))
+    return np.float32(scale) * (unit * np.float32(scalar))
+
+
+def read_lokr_adapter(adapter_dir: str, cfg: dict) -> Tuple[dict, Dict[str, dict]]:
+    """(header metadata, {"layers.0.self_attn.q_proj": dict(w1=, w2=, alpha=, scalar=, r=)}), a factor whole or
+    a pair; the modules are looked up by the names built from cfg's module list."""
+    path = os.path.join(adapter_dir, "lokr_weights.safetensors")
+    with open(path, "rb") as f:
+        meta = json.loads(f.read(struct.unpack("<Q", f.read(8))[0])).get("__metadata__", {})
+    raw = _read_safetensors_f32(path)
+    mods = {}
+    for i in range(cfg["num_hidden_layers"]):
+        for m in LORA_ALL_TARGETS:
+            n = lokr_name(f"layers.{i}.{m}")
+            t = {k[len(n) + 1:]: v.astype(np.float32) for k, v in raw.items() if k.split(".")[0] == n}
+            if not t:
+                continue
+            pick = lambda w: t[f"lokr_{w}"] if f"lokr_{w}" in t else (t[f"lokr_{w}_a"], t[f"lokr_{w}_b"])
+            w1, w2 = pick("w1"), pick("w2")
+            r = w2[0].shape[1] if isinstance(w2, tuple) else (w1[0].shape[1] if isinstance(w1, tuple) else 0)
+            mods[f"layers.{i}.{m}"] = dict(w1=w1, w2=w2, alpha=t["alpha"].reshape(()), r=r,
+                                           scalar=t["scalar"].reshape(()) if "scalar" in t else np.float32(1.0))
+    return meta, mods
+
+
+def merged_lokr_checkpoint(base_dir: str, adapter_dir: str, scale: float, out_dir: str) -> str:
+    """merged_checkpoint for a LoKr adapter: the targeted decoder weights are rne16(f32(W) + eff * lokr_delta)."""
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(base_dir, "config.json"), "r", encoding="utf-8") as f:
+        cfg_text = f.read()
+    with open(os.path.join(out_dir, "config.json"), "w", encoding="utf-8") as f:
+        f.write(cfg_text)
+    meta, mods = read_lokr_adapter(adapter_dir, json.loads(cfg_text))
+    rs = bool(json.loads(meta.get("lokr_config", "{}")).get("rs_lora"))
+    tensors = _read_safetensors_raw(os.path.join(base_dir, "model.safetensors"))
+    for name, m in mods.items():
+        key = f"decoder.{name}.weight"
+        dt, shape, words = tensors[key]
+        eff = lokr_eff(scale, m["alpha"], m["r"], rs, m["scalar"])
+        tensors[key] = (dt, shape, lora_merge_bits(words.reshape(shape), lokr_delta(m["w1"], m["w2"]), eff, dt).reshape(-1))
+    _write_safetensors_raw(os.path.join(out_dir, "model.safetensors"), tensors)
     return out_dir

@@ -190,6 +190,48 @@ __host__ __device__ inline int lora_fused_row(int map, int row_off, int half, in
 // any number of jobs (launches of up to 8 jobs each); jobs of one call must not write the same rows
 void launch_lora_merge(const LoraMergeJob* jobs, int n, hipStream_t s);
 
+// ------------------------------------------------- LoKr merge (kernels/lokr.hip)
+// The adapted 16-bit image for a LyCORIS LoKr module of a*c rows and b*d (= cols) columns: the delta is the
+// Kronecker product  dW[i*c + k][j*d + l] = w1[i][j] * W2[k][l]  and
+//   v = w1[i][j] * W2[k][l];  t = eff * v;  out = rne16(f32(base) + t)   (each operation rounded to f32 on its own),
+// where w1 [a][b] is stored (w1) or the product w1a [a][r1] . w1b [r1][b], and W2 [c][d] is stored (w2) or
+// w2a [c][r2] . w2b [r2][d]; a product entry is the chain  acc = 0; for j ascending: acc = acc + L[m][j] * R[j][n]
+// of LoraMergeJob (never contracted), so numpy restates all of it bit for bit (acestep_mi355x/synthetic.py
+// lokr_delta).  Rows, row maps, copy-through rows, in place and alignment are LoraMergeJob's.  A job whose factor
+// is a product needs the f32 workspace ws of lokr_ws_floats() floats, which launch_lokr_merge fills (the products,
+// once per job) before the merge reads it; jobs of one call must not share a workspace.
+struct LokrMergeJob {
+    int fmt = WF_BF16;  // WF_BF16 | WF_F16, of base and out
+    const uint16_t* base = nullptr;
+    int64_t ld_base = 0;
+    uint16_t* out = nullptr;
+    int64_t ld_out = 0;
+    int row0 = 0, rows = 0, cols = 0;
+    int a = 0, b = 0, c = 0, d = 0;  // a = 0: no module, the whole range is copy-through
+    const float* w1 = nullptr;   // [a][b], or null with
+    const float* w1a = nullptr;  // [a][r1]
+    const float* w1b = nullptr;  // [r1][b]
+    int r1 = 0;
+    const float* w2 = nullptr;   // [c][d], or null with
+    const float* w2a = nullptr;  // [c][r2]
+    const float* w2b = nullptr;  // [r2][d]
+    int r2 = 0;
+    float* ws = nullptr;
+    float eff = 0.f;
+    int map = LORA_ROWS_PLAIN;
+    int row_off = 0;
+    int half = 0;
+    bool copy_rest = false;
+};
+constexpr int LOKR_MAX_RANK = 1024;
+// floats of a job's workspace: W2 [c][d] when it is a product (rounded up to 4), then w1 [a][b] when it is one
+inline size_t lokr_ws_w1_offset(const LokrMergeJob& j) { return j.w2 ? 0 : (((size_t)j.c * j.d + 3) & ~size_t(3)); }
+inline size_t lokr_ws_floats(const LokrMergeJob& j) {
+    return j.a <= 0 ? 0 : lokr_ws_w1_offset(j) + (j.w1 ? 0 : (size_t)j.a * j.b);
+}
+// any number of jobs (launches of up to 8 jobs each); jobs of one call must not write the same rows
+void launch_lokr_merge(const LokrMergeJob* jobs, int n, hipStream_t s);
+
 // ------------------------------------------------- ggml-faithful quantized activations (kernels/gemm_a8.hip)
 // ggml's mul_mat against a quantized weight first converts the f32 activation rows to the weight's vec_dot_type
 // (Q8_0 blocks for Q8_0 weights, Q8_K for K-quants) and takes integer dot products per block

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "../kernels.h"
+#include "merge16.h"
 
 // the chain is never contracted into FMAs (the kernel files build with -ffp-contract=fast-honor-pragmas)
 #pragma clang fp contract(off)
@@ -31,21 +32,6 @@ struct LoraBatch {
     int end[8];        // exclusive prefix sums of (module + copy) tiles
     int n;
 };
-
-__device__ __forceinline__ uint16_t f32_to_bf16_rne(float f) {
-    uint32_t u = __float_as_uint(f);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 64u);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-__device__ __forceinline__ uint16_t f32_to_16(bool f16, float f) {
-    if (f16) return __builtin_bit_cast(uint16_t, (_Float16)f);
-    return f32_to_bf16_rne(f);
-}
-__device__ __forceinline__ float f16_to_f32(bool f16, uint16_t v) {
-    if (f16) return (float)__builtin_bit_cast(_Float16, v);
-    return __uint_as_float((uint32_t)v << 16);
-}
 
 __global__ void __launch_bounds__(256) lora_merge_kernel(LoraBatch b) {
     __shared__ __attribute__((aligned(16))) float As[RC][TC];

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "../kernels/attn_probs_host.h"  // empty under hipcc; the host build's launch_attn_probs
+#include "lokr.h"
 #include "lora.h"
 #include "operands.h"
 
@@ -553,19 +554,23 @@ void DitEngine::free_lora() {
     lora_a_.clear();
     lora_b_.clear();
     lora_.reset();
+    lokr_f_.clear();
+    lokr_ws_off_.clear();
+    lokr_ws_.release();
+    lokr_.reset();
     lora_scale_ = 0.f;
     lora_merge_ms_ = 0.0;
 }
 
 DitEngine::LoraInfo DitEngine::lora_info() const {
     LoraInfo i;
-    if (!lora_) return i;
+    if (!lora_ && !lokr_) return i;
     i.loaded = true;
     i.scale = lora_scale_;
-    i.lora_alpha = lora_->lora_alpha;
-    i.min_rank = lora_->min_rank;
-    i.max_rank = lora_->max_rank;
-    i.modules = (int)lora_->modules.size();
+    i.lora_alpha = lora_ ? lora_->lora_alpha : lokr_->modules[0].alpha;
+    i.min_rank = lora_ ? lora_->min_rank : lokr_->min_rank;
+    i.max_rank = lora_ ? lora_->max_rank : lokr_->max_rank;
+    i.modules = (int)(lora_ ? lora_->modules.size() : lokr_->modules.size());
     for (const auto& kv : images_.adapted)
         if (kv.second.p) {
             ++i.images;
@@ -584,16 +589,22 @@ void DitEngine::rebuild_lora_images(hipStream_t s) {
     images_.invalidate();
     images_.adapter_on = false;
     lora_merge_ms_ = 0.0;
-    if (!lora_ || lora_scale_ == 0.f) return;
+    if ((!lora_ && !lokr_) || lora_scale_ == 0.f) return;
 
     const DitModel& m = model_;
     const DitConfig& c = m.cfg;
     const int H = c.hidden, I = c.intermediate, qd = c.hq * c.head_dim, kd = c.hkv * c.head_dim;
     std::map<std::tuple<int, int, int>, int> index;
-    for (size_t i = 0; i < lora_->modules.size(); ++i) {
-        const LoraModule& lm = lora_->modules[i];
-        index[std::make_tuple(lm.layer, lm.block, lm.proj)] = (int)i;
-    }
+    if (lora_)
+        for (size_t i = 0; i < lora_->modules.size(); ++i) {
+            const LoraModule& lm = lora_->modules[i];
+            index[std::make_tuple(lm.layer, lm.block, lm.proj)] = (int)i;
+        }
+    else
+        for (size_t i = 0; i < lokr_->modules.size(); ++i) {
+            const LokrModule& km = lokr_->modules[i];
+            index[std::make_tuple(km.layer, km.block, km.proj)] = (int)i;
+        }
     struct Slot {  // one module's rows inside a fused matrix
         int map, row_off, half, rows_mod, mod;
     };
@@ -638,6 +649,7 @@ void DitEngine::rebuild_lora_images(hipStream_t s) {
 
     // allocate first (ensure() synchronises the device), then launch everything in stream order
     std::vector<LoraMergeJob> jobs;
+    std::vector<LokrMergeJob> kjobs;  // LoKr: the same rows, ranges and maps, the Kronecker factors for A / B
     std::vector<std::pair<const DevWeight*, uint16_t*>> expand;
     for (const auto& mt : mats) {
         const DevWeight& w = *mt.first;
@@ -672,6 +684,24 @@ void DitEngine::rebuild_lora_images(hipStream_t s) {
                 j.rows = sl.rows_mod;
                 j.copy_rest = sl.mod < 0;  // a module without an adapter: its rows are copied through
             }
+            if (lokr_) {
+                if (sl.mod < 0 && quantized) continue;  // in place: the rows are in the image already
+                LokrMergeJob kj;
+                kj.fmt = j.fmt, kj.base = j.base, kj.ld_base = j.ld_base, kj.out = j.out, kj.ld_out = j.ld_out;
+                kj.row0 = j.row0, kj.rows = j.rows, kj.cols = j.cols;
+                kj.map = j.map, kj.row_off = j.row_off, kj.half = j.half, kj.copy_rest = j.copy_rest;
+                if (sl.mod >= 0) {
+                    const LokrModule& km = lokr_->modules[sl.mod];
+                    ACEMI_CHECK(km.in == w.cols && km.out == sl.rows_mod, "lokr: module shape does not match the weight");
+                    const float* const* f = &lokr_f_[6 * (size_t)sl.mod];
+                    kj.a = km.a, kj.b = km.b, kj.c = km.c, kj.d = km.d, kj.r1 = km.r1, kj.r2 = km.r2;
+                    kj.w1 = f[0], kj.w1a = f[1], kj.w1b = f[2], kj.w2 = f[3], kj.w2a = f[4], kj.w2b = f[5];
+                    kj.ws = lokr_ws_.as<float>() + lokr_ws_off_[sl.mod];
+                    kj.eff = lora_scale_ * km.unit;
+                }
+                kjobs.push_back(kj);
+                continue;
+            }
             if (sl.mod >= 0) {
                 const LoraModule& lm = lora_->modules[sl.mod];
                 ACEMI_CHECK(lm.in == w.cols && lm.out == sl.rows_mod, "lora: module shape does not match the weight");
@@ -690,6 +720,7 @@ void DitEngine::rebuild_lora_images(hipStream_t s) {
     const auto t0 = std::chrono::steady_clock::now();
     for (const auto& e : expand) WeightImages::expand(*e.first, e.second, s);
     launch_lora_merge(jobs.data(), (int)jobs.size(), s);
+    launch_lokr_merge(kjobs.data(), (int)kjobs.size(), s);
     ACEMI_HIP(hipStreamSynchronize(s));
     lora_merge_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     images_.adapter_on = true;
@@ -699,6 +730,8 @@ void DitEngine::load_lora(const std::string& dir, float scale, int max_layers, h
     if (qact_)
         throw Unsupported("lora: the quantized-activation parity mode (ACE_MI_QUANT_ACT=q8) multiplies the block "
                           "weights themselves and cannot run an adapter");
+    const std::string lokr_file = lokr_weights_file(dir);
+    if (!lokr_file.empty()) return load_lokr(lokr_file, scale, max_layers, s);
     auto ad = std::make_unique<LoraAdapter>(read_lora_adapter(dir, model_.cfg, max_layers));  // throws: state unchanged
     ACEMI_HIP(hipDeviceSynchronize());
     free_lora();
@@ -731,8 +764,48 @@ void DitEngine::load_lora(const std::string& dir, float scale, int max_layers, h
     }
 }
 
+// A LyCORIS LoKr adapter (runtime/lokr.h): the stored factors in lora_ab_, the products' workspace in lokr_ws_.
+void DitEngine::load_lokr(const std::string& file, float scale, int max_layers, hipStream_t s) {
+    auto ad = std::make_unique<LokrAdapter>(read_lokr_adapter(file, model_.cfg, max_layers));  // throws: state unchanged
+    ACEMI_HIP(hipDeviceSynchronize());
+    free_lora();
+    size_t total = 0, ws = 0;
+    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
+    for (const LokrModule& km : ad->modules)
+        for (const auto& v : km.f) total += v.empty() ? 0 : al(v.size() * 4);
+    std::vector<char> host(total);
+    lora_ab_.ensure(total);
+    size_t off = 0;
+    for (LokrModule& km : ad->modules) {
+        for (auto& v : km.f) {
+            lokr_f_.push_back(v.empty() ? nullptr : reinterpret_cast<const float*>(lora_ab_.as<char>() + off));
+            if (v.empty()) continue;
+            std::memcpy(&host[off], v.data(), v.size() * 4);
+            off += al(v.size() * 4);
+            v = std::vector<float>();
+        }
+        LokrMergeJob shape;  // the workspace layout is the job's
+        shape.a = km.a, shape.b = km.b, shape.c = km.c, shape.d = km.d;
+        const float* const* f = &lokr_f_[lokr_f_.size() - 6];
+        shape.w1 = f[0], shape.w2 = f[3];
+        lokr_ws_off_.push_back(ws);
+        ws += (lokr_ws_floats(shape) + 63) & ~size_t(63);
+    }
+    lokr_ws_.ensure(ws * 4);
+    ACEMI_HIP(hipMemcpy(lora_ab_.p, host.data(), total, hipMemcpyHostToDevice));
+    ACEMI_HIP(hipDeviceSynchronize());  // null-stream copy: done before any stream reads it
+    lokr_ = std::move(ad);
+    lora_scale_ = scale;
+    try {
+        rebuild_lora_images(s);
+    } catch (...) {
+        free_lora();
+        throw;
+    }
+}
+
 void DitEngine::set_lora_scale(float scale, hipStream_t s) {
-    ACEMI_CHECK(lora_ != nullptr, "lora not loaded");
+    ACEMI_CHECK(lora_ != nullptr || lokr_ != nullptr, "lora not loaded");
     lora_scale_ = scale;
     rebuild_lora_images(s);
 }
@@ -747,27 +820,28 @@ void DitEngine::unload_lora(hipStream_t s) {
 // Host build of the runtime (no device compiler: the CPU tests' library, whose other launch_* are host loops too):
 // launch_lora_merge as plain loops with the arithmetic of kernels.h, on "device" memory that is host memory.  The
 // translation unit is compiled without FMA contraction, so each multiply and add below rounds on its own.
+static float merge_widen(int fmt, uint16_t b) {
+    if (fmt == WF_F16) return half_to_f32(b);
+    const uint32_t u = (uint32_t)b << 16;
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+static uint16_t merge_narrow(int fmt, float f) {
+    if (fmt == WF_F16) {
+        const _Float16 h = (_Float16)f;
+        uint16_t u;
+        std::memcpy(&u, &h, 2);
+        return u;
+    }
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 64u);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
 void launch_lora_merge(const LoraMergeJob* jobs, int n, hipStream_t) {
-    auto widen = [](int fmt, uint16_t b) {
-        if (fmt == WF_F16) return half_to_f32(b);
-        const uint32_t u = (uint32_t)b << 16;
-        float f;
-        std::memcpy(&f, &u, 4);
-        return f;
-    };
-    auto narrow = [](int fmt, float f) -> uint16_t {
-        if (fmt == WF_F16) {
-            const _Float16 h = (_Float16)f;
-            uint16_t u;
-            std::memcpy(&u, &h, 2);
-            return u;
-        }
-        uint32_t u;
-        std::memcpy(&u, &f, 4);
-        if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 64u);
-        u += 0x7fffu + ((u >> 16) & 1u);
-        return (uint16_t)(u >> 16);
-    };
     for (int ji = 0; ji < n; ++ji) {
         const LoraMergeJob& j = jobs[ji];
         ACEMI_CHECK((j.fmt == WF_BF16 || j.fmt == WF_F16) && j.base && j.out && j.rows > 0 && j.cols > 0 &&
@@ -788,7 +862,51 @@ void launch_lora_merge(const LoraMergeJob* jobs, int n, hipStream_t) {
                     acc = acc + p;
                 }
                 const float t = j.eff * acc;
-                dst[i] = narrow(j.fmt, widen(j.fmt, src[i]) + t);
+                dst[i] = merge_narrow(j.fmt, merge_widen(j.fmt, src[i]) + t);
+            }
+        }
+    }
+}
+
+// launch_lokr_merge the same way (kernels.h LokrMergeJob): the product factors as rank-ordered chains into the job's
+// workspace, then one rounded multiply w1 * W2, one by eff and one rounded add per weight.
+void launch_lokr_merge(const LokrMergeJob* jobs, int n, hipStream_t) {
+    auto product = [](const float* L, const float* R, float* out, int m, int nn, int r) {
+        for (int o = 0; o < m; ++o)
+            for (int i = 0; i < nn; ++i) {
+                volatile float acc = 0.f;
+                for (int k = 0; k < r; ++k) {
+                    const float p = L[(int64_t)o * r + k] * R[(int64_t)k * nn + i];
+                    acc = acc + p;
+                }
+                out[(int64_t)o * nn + i] = acc;
+            }
+    };
+    for (int ji = 0; ji < n; ++ji) {
+        const LokrMergeJob& j = jobs[ji];
+        ACEMI_CHECK((j.fmt == WF_BF16 || j.fmt == WF_F16) && j.base && j.out && j.rows > 0 && j.cols > 0 && j.a >= 0,
+                    "lokr_merge: bad job");
+        const float *w1 = j.w1, *W2 = j.w2;
+        if (j.a > 0) {
+            ACEMI_CHECK(j.b > 0 && j.c > 0 && j.d > 0 && (int64_t)j.b * j.d == j.cols && (j.w1 || (j.w1a && j.w1b && j.r1 > 0)) &&
+                            (j.w2 || (j.w2a && j.w2b && j.r2 > 0)) && (lokr_ws_floats(j) == 0 || j.ws),
+                        "lokr_merge: bad factors");
+            if (!W2) product(j.w2a, j.w2b, j.ws, j.c, j.d, j.r2), W2 = j.ws;
+            if (!w1) product(j.w1a, j.w1b, j.ws + lokr_ws_w1_offset(j), j.a, j.b, j.r1), w1 = j.ws + lokr_ws_w1_offset(j);
+        }
+        const int rows_mod = j.a * j.c;
+        for (int fr = j.row0; fr < j.row0 + j.rows; ++fr) {
+            const int o = lora_module_row(j.map, j.row_off, j.half, rows_mod, rows_mod, fr);
+            const uint16_t* src = j.base + (int64_t)fr * j.ld_base;
+            uint16_t* dst = j.out + (int64_t)fr * j.ld_out;
+            if (o < 0) {
+                if (j.copy_rest && src != dst) std::memmove(dst, src, (size_t)j.cols * 2);
+                continue;
+            }
+            for (int i = 0; i < j.cols; ++i) {
+                volatile float v = w1[(int64_t)(o / j.c) * j.b + i / j.d] * W2[(int64_t)(o % j.c) * j.d + i % j.d];
+                volatile float t = j.eff * v;
+                dst[i] = merge_narrow(j.fmt, merge_widen(j.fmt, src[i]) + t);
             }
         }
     }

@@ -20,6 +20,7 @@
 namespace acemi {
 
 struct LoraAdapter;  // runtime/lora.h
+struct LokrAdapter;  // runtime/lokr.h
 
 struct ForwardIO {
     int B = 1, T = 0, L = 0;
@@ -116,6 +117,10 @@ class DitEngine {
     // expanded to its bf16 image first and merged in place), which the GEMMs read from then on (weight_images.h): same
     // kernels, same launches, nothing per step.  A scale change rebuilds from the base weights and unload is exact.
     // All three block until the device is idle.  max_layers: ACE_GGML_DIT_MAX_LAYERS.
+    // load_lora also takes a LyCORIS LoKr adapter (runtime/lokr.h: a directory with lokr_weights.safetensors and no
+    // adapter_config.json, or that file): same images, built by launch_lokr_merge; it replaces a loaded LoRA adapter
+    // and the other way round, so the two are never applied together.  For LoKr, LoraInfo's ranks are those of the
+    // low-rank factors (0: every factor stored whole) and lora_alpha is the first module's alpha.
     struct LoraInfo {
         bool loaded = false;
         float scale = 0.f, lora_alpha = 0.f;
@@ -126,7 +131,7 @@ class DitEngine {
     void load_lora(const std::string& dir, float scale, int max_layers, hipStream_t s);
     void set_lora_scale(float scale, hipStream_t s);
     void unload_lora(hipStream_t s);
-    bool lora_loaded() const { return lora_ != nullptr; }
+    bool lora_loaded() const { return lora_ != nullptr || lokr_ != nullptr; }
     LoraInfo lora_info() const;
 
    private:
@@ -191,6 +196,13 @@ class DitEngine {
     std::unique_ptr<LoraAdapter> lora_;
     std::vector<const float*> lora_a_, lora_b_;  // device A / B of lora_->modules[i]
     DevBuf lora_ab_;
+    // LoKr state: the factors of lokr_->modules[i] at lokr_f_[6 * i + {w1, w1a, w1b, w2, w2a, w2b}] (null: not
+    // stored) inside lora_ab_, and the f32 workspace of the products (lokr_ws_, module i at lokr_ws_off_[i])
+    std::unique_ptr<LokrAdapter> lokr_;
+    std::vector<const float*> lokr_f_;
+    std::vector<size_t> lokr_ws_off_;
+    DevBuf lokr_ws_;
+    void load_lokr(const std::string& file, float scale, int max_layers, hipStream_t s);
     float lora_scale_ = 0.f;
     double lora_merge_ms_ = 0.0;
     void rebuild_lora_images(hipStream_t s);

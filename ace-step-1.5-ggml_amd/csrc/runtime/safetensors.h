@@ -58,6 +58,7 @@ struct StFile {
     std::string path;
     uint64_t data_offset = 0;
     std::map<std::string, StTensor> tensors;
+    std::map<std::string, std::string> metadata;  // the header's __metadata__ (string values)
 
     void open(const std::string& p) {
         path = p;
@@ -82,7 +83,12 @@ struct StFile {
         }
         if (root.kind != Json::Object) throw IoError("invalid safetensors header");
         for (const auto& kv : root.obj) {
-            if (kv.first == "__metadata__") continue;
+            if (kv.first == "__metadata__") {
+                if (kv.second.kind == Json::Object)
+                    for (const auto& m : kv.second.obj)
+                        if (m.second.kind == Json::String) metadata[m.first] = m.second.as_str();
+                continue;
+            }
             StTensor t;
             t.dtype = kv.second.at("dtype").as_str();
             for (const auto& d : kv.second.at("shape").arr) t.shape.push_back(d.as_int());

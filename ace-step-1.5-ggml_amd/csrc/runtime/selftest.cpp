@@ -602,6 +602,79 @@ ace_ggml_status ace_mi_kernel_lora_merge(int32_t fmt, int32_t total_rows, int32_
     return ACE_GGML_OK;
 }
 
+// LoKr merge kernels: n_jobs jobs of one launch_lokr_merge call on one host matrix pair (include/acestep_mi355x_selftest.h).
+ace_ggml_status ace_mi_kernel_lokr_merge(int32_t fmt, int32_t total_rows, int32_t cols, int32_t ld_base, int32_t ld_out,
+                                         const uint16_t* base, uint16_t* out, const ace_mi_lokr_job* jobs,
+                                         int32_t n_jobs) {
+    using namespace acemi;
+    if (!out || !jobs || n_jobs <= 0 || total_rows <= 0 || cols <= 0 || ld_out < cols || (base && ld_base < cols) ||
+        (fmt != 0 && fmt != 1))
+        return ACE_GGML_ERR_INVALID_ARG;
+    for (int i = 0; i < n_jobs; ++i) {  // every row a job may touch lies inside the host matrices
+        const ace_mi_lokr_job& j = jobs[i];
+        if (j.row0 < 0 || j.rows <= 0 || j.row0 + j.rows > total_rows || j.a < 0) return ACE_GGML_ERR_INVALID_ARG;
+        if (j.a > 0 && (j.b <= 0 || j.c <= 0 || j.d <= 0 || (int64_t)j.b * j.d != cols ||
+                        !(j.w1 || (j.w1a && j.w1b && j.r1 > 0)) || !(j.w2 || (j.w2a && j.w2b && j.r2 > 0))))
+            return ACE_GGML_ERR_INVALID_ARG;
+    }
+    try {
+        const size_t nb = (size_t)total_rows * (base ? ld_base : ld_out) * 2, no = (size_t)total_rows * ld_out * 2;
+        DevMem dbase(base, base ? nb : 16), dout(out, no);
+        std::vector<std::unique_ptr<DevMem>> mem;
+        auto up = [&](const float* h, size_t n) -> const float* {
+            if (!h) return nullptr;
+            mem.emplace_back(new DevMem(h, n * 4));
+            return mem.back()->as<float>();
+        };
+        std::vector<LokrMergeJob> lj(n_jobs);
+        for (int i = 0; i < n_jobs; ++i) {
+            const ace_mi_lokr_job& j = jobs[i];
+            LokrMergeJob& d = lj[i];
+            d.fmt = fmt == 1 ? WF_F16 : WF_BF16;
+            d.base = base ? dbase.as<uint16_t>() : dout.as<uint16_t>();
+            d.ld_base = base ? ld_base : ld_out;
+            d.out = dout.as<uint16_t>();
+            d.ld_out = ld_out;
+            d.row0 = j.row0;
+            d.rows = j.rows;
+            d.cols = cols;
+            d.eff = j.eff;
+            d.map = j.map;
+            d.row_off = j.row_off;
+            d.half = j.half;
+            d.copy_rest = j.copy_rest != 0;
+            if (j.a <= 0) continue;
+            d.a = j.a, d.b = j.b, d.c = j.c, d.d = j.d;
+            if (j.w1) {
+                d.w1 = up(j.w1, (size_t)j.a * j.b);
+            } else {
+                d.r1 = j.r1;
+                d.w1a = up(j.w1a, (size_t)j.a * j.r1);
+                d.w1b = up(j.w1b, (size_t)j.r1 * j.b);
+            }
+            if (j.w2) {
+                d.w2 = up(j.w2, (size_t)j.c * j.d);
+            } else {
+                d.r2 = j.r2;
+                d.w2a = up(j.w2a, (size_t)j.c * j.r2);
+                d.w2b = up(j.w2b, (size_t)j.r2 * j.d);
+            }
+            if (lokr_ws_floats(d) > 0) {
+                mem.emplace_back(new DevMem(lokr_ws_floats(d) * 4));
+                d.ws = mem.back()->as<float>();
+            }
+        }
+        ACEMI_HIP(hipDeviceSynchronize());
+        launch_lokr_merge(lj.data(), n_jobs, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dout.to_host(out, no);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lokr_merge: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
 // Dequant-fused GEMM on ggml block rows W [N][K]: out = A(bf16) . bf16(dequant(W))^T (+ bias).
 ace_ggml_status ace_mi_kernel_gemm_q(int32_t qtype, int32_t epi, int32_t variant, int32_t M, int32_t N, int32_t K,
                                      const uint16_t* A, const uint8_t* W_blocks, const float* bias, float* out_f32,

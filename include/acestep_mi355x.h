@@ -134,7 +134,10 @@ typedef struct ace_mi_lora_info {
     int64_t image_bytes;     /* device memory of the images */
     double merge_ms;         /* host wall time of the last image build (launch to completion) */
 } ace_mi_lora_info;
-/* Load (replacing any previous adapter) at strength `scale`. */
+/* Load (replacing any previous adapter) at strength `scale`.  `adapter_dir` may also be a LyCORIS LoKr adapter as the
+ * reference trainer saves it (acestep/training/lokr_utils.py): a directory that holds lokr_weights.safetensors and no
+ * adapter_config.json, or that file's path.  Its delta is kron(w1, w2) * unit (INTEGRATION "LoKr format"); the info
+ * struct then reports the low-rank factors' ranks (0: stored whole) and the first module's alpha. */
 ACE_GGML_API ace_ggml_status ace_mi_dit_load_lora(ace_ggml_context* ctx, const char* adapter_dir, float scale);
 /* Rebuild the images from the base weights at a new strength; 0 routes every matrix back to its base weights and
  * keeps the adapter resident.  ACE_GGML_ERR "lora not loaded" without an adapter. */

@@ -133,6 +133,26 @@ typedef struct ace_mi_lora_job {
 ACE_GGML_API ace_ggml_status ace_mi_kernel_lora_merge(int32_t fmt, int32_t total_rows, int32_t cols, int32_t ld_base,
                                                       int32_t ld_out, const uint16_t* base, uint16_t* out,
                                                       const ace_mi_lora_job* jobs, int32_t n_jobs);
+/* LoKr merge kernels (launch_lokr_merge, csrc/kernels.h): as ace_mi_kernel_lora_merge, with the Kronecker delta
+ * dW[i*c + k][j*d + l] = w1[i][j] * W2[k][l] of a module of a*c rows and b*d = cols columns.  w1 [a][b] is given
+ * (w1) or is the product w1a [a][r1] . w1b [r1][b] (w1 NULL); W2 [c][d] is given (w2) or is w2a [c][r2] . w2b [r2][d]
+ * (w2 NULL); all f32 host arrays.  a = 0 is a copy-only job.  out = rne16(f32(base) + eff * (w1 * W2)), every
+ * operation rounded to f32 on its own and the products rank-ordered chains. */
+typedef struct ace_mi_lokr_job {
+    int32_t row0, rows;
+    int32_t a, b, c, d, r1, r2;
+    const float* w1;
+    const float* w1a;
+    const float* w1b;
+    const float* w2;
+    const float* w2a;
+    const float* w2b;
+    float eff;
+    int32_t map, row_off, half, copy_rest;
+} ace_mi_lokr_job;
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lokr_merge(int32_t fmt, int32_t total_rows, int32_t cols, int32_t ld_base,
+                                                      int32_t ld_out, const uint16_t* base, uint16_t* out,
+                                                      const ace_mi_lokr_job* jobs, int32_t n_jobs);
 /* ---- LM decode kernels (csrc/kernels/lm_decode.hip through launch_lm_* of csrc/kernels.h; csrc/runtime/selftest_lm.cpp).
  * One launch_lm_* call each on host buffers; INVALID_ARG, before any allocation, for what the launch entry refuses or
  * what does not fit the host buffers.  16-bit words are raw bf16 (type / fmt 0) or fp16 (1).
