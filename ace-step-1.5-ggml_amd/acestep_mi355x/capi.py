@@ -55,7 +55,8 @@ SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_ker
                     "ace_mi_gemm_resolve", "ace_mi_gemm_variant_row", "ace_mi_gemm_variant_arg_ok",
                     "ace_mi_kernel_attn_policy", "ace_mi_attn_plan", "ace_mi_attn_plan_block", "ace_mi_attn_plan_tiles",
                     "ace_mi_kernel_lm_skinny", "ace_mi_kernel_lm_embed", "ace_mi_kernel_lm_qkv_post",
-                    "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention", "ace_mi_kernel_lm_skinny_q",
+                    "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention", "ace_mi_kernel_lm_attention_shared",
+                    "ace_mi_kernel_lm_skinny_q",
                     "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_select", "ace_mi_kernel_lm_cache_fanout",
                     "ace_mi_kernel_conv_gemm", "ace_mi_kernel_conv_out", "ace_mi_kernel_pack_f16",
                     "ace_mi_rope_table", "ace_mi_rope_table_steps")
@@ -1204,13 +1205,14 @@ def _bind_lm_kernels(lib):
     lib.ace_mi_kernel_lm_qkv_post.argtypes = [i32] * 6 + [f32, fp, fp, fp, fp, fp, ip, fp, u16p, u16p, ip]
     lib.ace_mi_kernel_lm_prefill_kv.argtypes = [i32] * 6 + [f32, fp, fp, fp, fp, ip, u16p, u16p, ip]
     lib.ace_mi_kernel_lm_attention.argtypes = [i32] * 6 + [f32, fp, u16p, u16p, ip, u16p]
+    lib.ace_mi_kernel_lm_attention_shared.argtypes = [i32] * 8 + [f32, fp, u16p, u16p, ip, u16p]
     u8p = ctypes.POINTER(ctypes.c_uint8)
     lib.ace_mi_kernel_lm_skinny_q.argtypes = [i32] * 8 + [u16p, u8p, fp, u16p, ip]
     lib.ace_mi_kernel_lm_embed_q.argtypes = [i32] * 4 + [u8p, ip, fp]
     lib.ace_mi_kernel_lm_select.argtypes = [ctypes.POINTER(AceMiKernelLmSelectArgs)]
     lib.ace_mi_kernel_lm_cache_fanout.argtypes = [i32] * 7 + [u16p, u16p, ip, u16p, u16p, ip]
-    for name in ("skinny", "embed", "qkv_post", "prefill_kv", "attention", "skinny_q", "embed_q", "select",
-                 "cache_fanout"):
+    for name in ("skinny", "embed", "qkv_post", "prefill_kv", "attention", "attention_shared", "skinny_q", "embed_q",
+                 "select", "cache_fanout"):
         getattr(lib, "ace_mi_kernel_lm_" + name).restype = ctypes.c_int
     return lib
 
@@ -1367,6 +1369,25 @@ def kernel_lm_attention(q: np.ndarray, k_cache: np.ndarray, v_cache: np.ndarray,
     st = lib.ace_mi_kernel_lm_attention(out_type, B, hq, kc.shape[1], kc.shape[2], nk, scale, _fptr(qq), _u16ptr(kc),
                                         _u16ptr(vc), _iptr(km), _u16ptr(out))
     _lm_status("attention", st)
+    return out
+
+
+def kernel_lm_attention_shared(q: np.ndarray, k_cache: np.ndarray, v_cache: np.ndarray, key_mask: np.ndarray, nk: int,
+                               scale: float, n_shared: int, group_size: int, out_type: int = 0, lib=None) -> np.ndarray:
+    """launch_lm_attention_shared on kernel_lm_attention's arrays: the B sequences are B / group_size groups whose
+    members hold the K, V and key_mask rows of the group's first sequence bit for bit at positions [0, n_shared)."""
+    lib = _lm_lib(lib)
+    qq = np.ascontiguousarray(q, dtype=np.float32)
+    kc, vc = (np.ascontiguousarray(a, dtype=np.uint16) for a in (k_cache, v_cache))
+    km = np.ascontiguousarray(key_mask, dtype=np.int32)
+    B, hq = qq.shape[0], qq.shape[1]
+    if group_size >= 1 and B % group_size != 0:
+        raise ValueError("kernel_lm_attention_shared: the batch is not a whole number of groups")
+    out = np.full((B, hq, 128), 0x7fff, dtype=np.uint16)
+    st = lib.ace_mi_kernel_lm_attention_shared(out_type, B // group_size if group_size >= 1 else 0, group_size, hq,
+                                               kc.shape[1], kc.shape[2], nk, n_shared, scale, _fptr(qq), _u16ptr(kc),
+                                               _u16ptr(vc), _iptr(km), _u16ptr(out))
+    _lm_status("attention_shared", st)
     return out
 
 

@@ -510,11 +510,34 @@ struct LmAttnArgs {
     uint16_t* out = nullptr;  // [B][hq*128] in the act type
     float* part = nullptr;    // lm_attn_part_floats() floats when nk > LM_SPLIT_KEYS
     int n_split = 1;          // set by launch_lm_attention
+    // launch_lm_attention_shared only: sequences g * group_size + s, s < group_size, hold the K, V and key_mask rows of
+    // sequence g * group_size bit for bit at positions [0, n_shared)
+    int n_shared = 0, group_size = 1;
+    int shared_items = 0;  // items per shared workgroup, 2 / 4 / 8; 0 = lm_attn_shared_items (other values: measuring)
 };
 size_t lm_attn_part_floats(int B, int hq, int nk);
 // out = softmax(scale q.k over the keys with key_mask != 0) . V; a masked key's K and V never reach the result, slots
 // >= nk are not read, and a sequence whose keys are all masked gets exactly +0 in every output word of either type.
 void launch_lm_attention(ActType out_t, const LmAttnArgs& a, int B, int hq, hipStream_t s);
+// The same output, bit for bit, for a cache with a shared prefix (a.n_shared, a.group_size): the key ranges wholly
+// inside [0, n_shared) are read once per group, from its first sequence, for all of its items; the other ranges run
+// launch_lm_attention's workgroups in the same launch.  B % group_size == 0 and n_shared <= nk - 1 (the newest key is
+// never shared); n_shared < LM_SPLIT_KEYS, group_size == 1 or nk <= LM_SPLIT_KEYS: launch_lm_attention itself.
+void launch_lm_attention_shared(ActType out_t, const LmAttnArgs& a, int B, int hq, hipStream_t s);
+// items served by one shared workgroup: the smallest of 2, 4, 8 that holds the group, while items x rep <= 16 rows
+inline int lm_attn_shared_items(int group_size, int rep) {
+    const int fit = group_size <= 2 ? 2 : (group_size <= 4 ? 4 : 8);
+    return fit * rep <= 16 ? fit : 16 / rep;
+}
+// what launch_lm_attention_shared checks beyond launch_lm_attention's conditions; returns the items per workgroup
+inline int lm_attn_shared_check(const LmAttnArgs& a, int B, int rep) {
+    ACEMI_CHECK(a.group_size >= 1 && B % a.group_size == 0, "lm_attention_shared: the batch is not a whole number of groups");
+    ACEMI_CHECK(a.n_shared >= 0 && a.n_shared <= a.nk - 1, "lm_attention_shared: the newest key is never shared");
+    const int items = a.shared_items ? a.shared_items : lm_attn_shared_items(a.group_size, rep);
+    ACEMI_CHECK((items == 2 || items == 4 || items == 8) && items * rep <= 16,
+                "lm_attention_shared: items per workgroup must be 2, 4 or 8 and items x GQA ratio at most 16");
+    return items;
+}
 
 // ------------------------------------------------------------ LM cache fan-out (kernels/lm_fanout.hip)
 // A prefilled cache of G = 1 or 2 sequences re-laid for G * S sequences: destination sequence g * S + s is a bit copy of

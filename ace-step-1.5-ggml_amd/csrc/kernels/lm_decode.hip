@@ -16,6 +16,8 @@
 //                       share one read of K and V; scores, f32 softmax and P.V over up to LM_SPLIT_KEYS keys.
 //                       More keys: one workgroup per range of LM_SPLIT_KEYS writes (m, l, unnormalised O) and
 //                       lm_attn_merge_kernel joins the ranges in ascending order (log-sum-exp), deterministically.
+//   lm_attn_shared_kernel the same records for sequences in groups that share a prefix (the cache after a fan-out):
+//                       the ranges inside the prefix are read once per group and serve up to 16 query rows.
 //
 // KV cache: K and V [layer][B][hkv][capacity][128] fp16 (saturated to the fp16 range), key mask [B][capacity] int32.
 #include <hip/hip_runtime.h>
@@ -230,26 +232,34 @@ __global__ void __launch_bounds__(64) lm_prefill_kv_kernel(LmQkvPostArgs a, int 
 // ------------------------------------------------------------------ decode attention
 __device__ __forceinline__ void unpack8_f16(const uint4& w, float (&f)[8]) { unpack8<true>(w, f); }
 
-template <int REP, bool F16OUT>
-__global__ void __launch_bounds__(256) lm_attn_kernel(LmAttnArgs a) {
-    __shared__ float sc[REP][LM_SPLIT_KEYS];
-    __shared__ float red[4][REP][LM_D];
-    __shared__ float stat[REP][4];
-    const int sp = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
+// One key range (sp) of one kv head (h) for ROWS = items x REP query rows that all attend to the K, V and mask rows of
+// sequence b_kv: row r is head h * REP + r % REP of sequence b_q0 + r / REP.  A thread loads each K (then V) word once
+// and keeps it in registers across the loop over the rows, so the range is read once however many rows it serves.
+// n_items < ROWS / REP (a ragged last chunk): the rows past it recompute the last item and write nothing.
+// lm_attn_kernel is the case ROWS = REP, b_kv = b_q0: whatever ROWS is, a row's sums are these same f32 operations in
+// this same association (the 8-element fma chain and xor-8/4/2/1 butterfly of a score, expf(s - m), the 64-lane
+// butterfly and (stat0 + stat1) + (stat2 + stat3) of l, keys kg, kg + 16, ... ascending by fma, xor-16/32 and
+// (red0 + red1) + (red2 + red3) of O), so its record does not depend on which rows share the workgroup.
+// LDS: sc [ROWS][LM_SPLIT_KEYS], red [4][ROWS][LM_D], stat [ROWS][4].
+template <int ROWS, int REP, bool F16OUT>
+__device__ __forceinline__ void lm_attn_range(const LmAttnArgs& a, int sp, int h, int b_kv, int b_q0, int n_items,
+                                              float* __restrict__ sc, float* __restrict__ red,
+                                              float* __restrict__ stat) {
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int sub = tid & 15, kg = tid >> 4;
     const int k0 = sp * LM_SPLIT_KEYS;
     const int cnt = min(a.nk - k0, LM_SPLIT_KEYS);
     const int hq = a.hkv * REP;
-    const int64_t base = (((int64_t)b * a.hkv + h) * a.capacity + k0) * LM_D + sub * 8;
+    const int64_t base = (((int64_t)b_kv * a.hkv + h) * a.capacity + k0) * LM_D + sub * 8;
     const uint16_t* K = a.k_cache + base;
     const uint16_t* V = a.v_cache + base;
-    const int32_t* km = a.key_mask + (int64_t)b * a.capacity + k0;
+    const int32_t* km = a.key_mask + (int64_t)b_kv * a.capacity + k0;
 
-    float q[REP][8];
+    float q[ROWS][8];
 #pragma unroll
-    for (int r = 0; r < REP; ++r) {
-        const float* qp = a.q + ((int64_t)b * hq + h * REP + r) * LM_D + sub * 8;
+    for (int r = 0; r < ROWS; ++r) {
+        const int b = b_q0 + min(r / REP, n_items - 1);
+        const float* qp = a.q + ((int64_t)b * hq + h * REP + r % REP) * LM_D + sub * 8;
         const float4 q0 = *(const float4*)qp, q1 = *(const float4*)(qp + 4);
         q[r][0] = q0.x, q[r][1] = q0.y, q[r][2] = q0.z, q[r][3] = q0.w;
         q[r][4] = q1.x, q[r][5] = q1.y, q[r][6] = q1.z, q[r][7] = q1.w;
@@ -260,85 +270,141 @@ __global__ void __launch_bounds__(256) lm_attn_kernel(LmAttnArgs a) {
         const bool in = j < cnt;
         float kf[8];
         unpack8_f16(in ? *(const uint4*)(K + (int64_t)j * LM_D) : make_uint4(0, 0, 0, 0), kf);
+        const bool on = in && km[in ? j : 0] != 0;
 #pragma unroll
-        for (int r = 0; r < REP; ++r) {
+        for (int r = 0; r < ROWS; ++r) {
             float s = 0.f;
 #pragma unroll
             for (int i = 0; i < 8; ++i) s = fmaf(q[r][i], kf[i], s);
 #pragma unroll
             for (int o = 8; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-            if (in && sub == 0) sc[r][j] = km[j] != 0 ? s * a.scale : -INFINITY;
+            if (in && sub == 0) sc[r * LM_SPLIT_KEYS + j] = on ? s * a.scale : -INFINITY;
         }
     }
     __syncthreads();
     // softmax statistics of the range: thread t owns key t
-    float mloc[REP], p[REP];
+    float mloc[ROWS], p[ROWS];
 #pragma unroll
-    for (int r = 0; r < REP; ++r) {
-        float m = tid < cnt ? sc[r][tid] : -INFINITY;
+    for (int r = 0; r < ROWS; ++r) {
+        float m = tid < cnt ? sc[r * LM_SPLIT_KEYS + tid] : -INFINITY;
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-        if (lane == 0) stat[r][wave] = m;
+        if (lane == 0) stat[r * 4 + wave] = m;
     }
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < REP; ++r) {
-        mloc[r] = fmaxf(fmaxf(stat[r][0], stat[r][1]), fmaxf(stat[r][2], stat[r][3]));
-        const float s = tid < cnt ? sc[r][tid] : -INFINITY;
+    for (int r = 0; r < ROWS; ++r) {
+        mloc[r] = fmaxf(fmaxf(stat[r * 4 + 0], stat[r * 4 + 1]), fmaxf(stat[r * 4 + 2], stat[r * 4 + 3]));
+        const float s = tid < cnt ? sc[r * LM_SPLIT_KEYS + tid] : -INFINITY;
         p[r] = (s == -INFINITY) ? 0.f : expf(s - mloc[r]);
     }
     __syncthreads();  // stat and sc are rewritten below
-    float lsum[REP];
+    float lsum[ROWS];
 #pragma unroll
-    for (int r = 0; r < REP; ++r) {
-        if (tid < cnt) sc[r][tid] = p[r];
+    for (int r = 0; r < ROWS; ++r) {
+        if (tid < cnt) sc[r * LM_SPLIT_KEYS + tid] = p[r];
         const float l = wave_sum(p[r]);
-        if (lane == 0) stat[r][wave] = l;
+        if (lane == 0) stat[r * 4 + wave] = l;
     }
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < REP; ++r) lsum[r] = (stat[r][0] + stat[r][1]) + (stat[r][2] + stat[r][3]);
+    for (int r = 0; r < ROWS; ++r) lsum[r] = (stat[r * 4 + 0] + stat[r * 4 + 1]) + (stat[r * 4 + 2] + stat[r * 4 + 3]);
     // P.V: thread (kg, sub) sums its keys j = kg, kg + 16, ... in ascending order
-    float acc[REP][8];
+    float acc[ROWS][8];
 #pragma unroll
-    for (int r = 0; r < REP; ++r)
+    for (int r = 0; r < ROWS; ++r)
 #pragma unroll
         for (int i = 0; i < 8; ++i) acc[r][i] = 0.f;
     for (int j = kg; j < cnt; j += 16) {
         float vf[8];
         unpack8_f16(*(const uint4*)(V + (int64_t)j * LM_D), vf);
 #pragma unroll
-        for (int r = 0; r < REP; ++r) {
-            const float pj = sc[r][j];
+        for (int r = 0; r < ROWS; ++r) {
+            const float pj = sc[r * LM_SPLIT_KEYS + j];
 #pragma unroll
             for (int i = 0; i < 8; ++i) acc[r][i] = fmaf(pj, vf[i], acc[r][i]);
         }
     }
 #pragma unroll
-    for (int r = 0; r < REP; ++r)
+    for (int r = 0; r < ROWS; ++r)
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             float v = acc[r][i];
             v += __shfl_xor(v, 16);
             v += __shfl_xor(v, 32);
-            if (lane < 16) red[wave][r][sub * 8 + i] = v;
+            if (lane < 16) red[(wave * ROWS + r) * LM_D + sub * 8 + i] = v;
         }
     __syncthreads();
-    for (int e = tid; e < REP * LM_D; e += 256) {
-        const int r = e / LM_D, d = e % LM_D;
-        const float o = (red[0][r][d] + red[1][r][d]) + (red[2][r][d] + red[3][r][d]);
-        const int head = h * REP + r;
+    // thread (t >> 7, t & 127) joins the four waves of rows t >> 7, (t >> 7) + 2, ...
+    const int d = tid & (LM_D - 1);
+#pragma unroll
+    for (int r0 = 0; r0 < ROWS; r0 += 2) {
+        const bool odd = tid >= LM_D;
+        const int r = odd ? r0 + 1 : r0;
+        if (r >= ROWS || r / REP >= n_items) continue;
+        const float m_r = odd ? mloc[r0 + 1 < ROWS ? r0 + 1 : r0] : mloc[r0];
+        const float l_r = odd ? lsum[r0 + 1 < ROWS ? r0 + 1 : r0] : lsum[r0];
+        const float o = (red[(0 * ROWS + r) * LM_D + d] + red[(1 * ROWS + r) * LM_D + d]) +
+                        (red[(2 * ROWS + r) * LM_D + d] + red[(3 * ROWS + r) * LM_D + d]);
+        const int b = b_q0 + r / REP, head = h * REP + r % REP;
         if (a.n_split == 1) {
-            const float v = lsum[r] > 0.f ? o / lsum[r] : 0.f;
+            const float v = l_r > 0.f ? o / l_r : 0.f;
             a.out[((int64_t)b * hq + head) * LM_D + d] = to_act<F16OUT>(v);
         } else {
             float* part = a.part + (((int64_t)b * hq + head) * a.n_split + sp) * (LM_D + 2);
             part[2 + d] = o;
             if (d == 0) {
-                part[0] = mloc[r];
-                part[1] = lsum[r];
+                part[0] = m_r;
+                part[1] = l_r;
             }
         }
+    }
+}
+
+template <int REP, bool F16OUT>
+__global__ void __launch_bounds__(256) lm_attn_kernel(LmAttnArgs a) {
+    __shared__ float sc[REP * LM_SPLIT_KEYS];
+    __shared__ float red[4 * REP * LM_D];
+    __shared__ float stat[REP * 4];
+    const int b = blockIdx.z;
+    lm_attn_range<REP, REP, F16OUT>(a, blockIdx.x, blockIdx.y, b, b, 1, sc, red, stat);
+}
+
+// Decode attention over a cache whose B sequences come in groups of S = a.group_size that hold bit-identical K, V and
+// mask rows at positions [0, a.n_shared) (the state after LmEngine::fanout).  One launch, two kinds of workgroup:
+//   workgroups [0, n_shared_wg)  one per (shared range, kv head, group, chunk of ITEMS items): the n_sh = n_shared /
+//                                LM_SPLIT_KEYS ranges wholly inside the shared prefix are read from the group's first
+//                                sequence alone, once, for the ITEMS x REP query rows of the chunk;
+//   the rest                     one per (remaining range, kv head, sequence), lm_attn_kernel's workgroup: the range
+//                                that straddles n_shared and the tail each sequence wrote itself.
+// Both write lm_attn_kernel's (m, l, unnormalised O) records, bit for bit (lm_attn_range), and lm_attn_merge_kernel
+// joins them: a layer costs the two launches it cost before, and item s of a group gets what a one-item run gets.
+// That identity is why the rows are not fed to MFMA: a matrix instruction accumulates in an order of its own, the
+// loop's token-for-token promise (include/acestep_mi355x.h, the fan-out section) is worth more than the FLOPs of a
+// kernel bound by bytes and latency, and 16 rows x 8 fmas per loaded word already hide behind the load.
+// n_split > 1 here, so the output type is the merge kernel's alone.
+template <int ITEMS, int REP>
+__global__ void __launch_bounds__(256) lm_attn_shared_kernel(LmAttnArgs a, int n_sh, int n_chunks, int n_shared_wg) {
+    constexpr int ROWS = ITEMS * REP;
+    __shared__ float sc[ROWS * LM_SPLIT_KEYS];
+    __shared__ float red[4 * ROWS * LM_D];
+    __shared__ float stat[ROWS * 4];
+    int w = blockIdx.x;
+    if (w < n_shared_wg) {  // workgroup-uniform
+        const int sp = w % n_sh;
+        w /= n_sh;
+        const int h = w % a.hkv;
+        w /= a.hkv;
+        const int c = w % n_chunks, first = (w / n_chunks) * a.group_size;
+        lm_attn_range<ROWS, REP, false>(a, sp, h, first, first + c * ITEMS, min(ITEMS, a.group_size - c * ITEMS), sc, red,
+                                        stat);
+    } else {
+        w -= n_shared_wg;
+        const int n_rest = a.n_split - n_sh;
+        const int sp = n_sh + w % n_rest;
+        w /= n_rest;
+        const int b = w / a.hkv;
+        lm_attn_range<REP, REP, false>(a, sp, w % a.hkv, b, b, 1, sc, red, stat);
     }
 }
 
@@ -411,8 +477,8 @@ size_t lm_attn_part_floats(int B, int hq, int nk) {
     return (size_t)B * hq * ceil_div(nk, LM_SPLIT_KEYS) * (LM_D + 2);
 }
 
-void launch_lm_attention(ActType out_t, const LmAttnArgs& a0, int B, int hq, hipStream_t s) {
-    LmAttnArgs a = a0;
+// the conditions of both attention launchers; sets a.n_split and returns the GQA ratio
+static int lm_attn_check(LmAttnArgs& a, int B, int hq) {
     ACEMI_CHECK(B >= 1 && B <= LM_MAX_BATCH && a.hkv >= 1 && hq % a.hkv == 0 && a.nk >= 1 && a.nk <= a.capacity &&
                     a.q && a.k_cache && a.v_cache && a.key_mask && a.out,
                 "lm_attention: bad arguments");
@@ -420,6 +486,45 @@ void launch_lm_attention(ActType out_t, const LmAttnArgs& a0, int B, int hq, hip
     ACEMI_CHECK(rep == 1 || rep == 2 || rep == 4, "lm_attention: GQA ratio must be 1, 2 or 4");
     a.n_split = (int)ceil_div(a.nk, LM_SPLIT_KEYS);
     ACEMI_CHECK(a.n_split == 1 || a.part, "lm_attention: split workspace missing");
+    return rep;
+}
+
+static void lm_attn_merge(bool f16, const LmAttnArgs& a, int B, int hq, hipStream_t s) {
+    if (f16)
+        hipLaunchKernelGGL(lm_attn_merge_kernel<true>, dim3(hq, B), dim3(128), 0, s, a.part, hq, a.n_split, a.out);
+    else
+        hipLaunchKernelGGL(lm_attn_merge_kernel<false>, dim3(hq, B), dim3(128), 0, s, a.part, hq, a.n_split, a.out);
+    ACEMI_HIP(hipGetLastError());
+}
+
+void launch_lm_attention_shared(ActType out_t, const LmAttnArgs& a0, int B, int hq, hipStream_t s) {
+    LmAttnArgs a = a0;
+    const int rep = lm_attn_check(a, B, hq);
+    const int items = lm_attn_shared_check(a, B, rep), S = a.group_size;
+    const int n_sh = a.n_shared / LM_SPLIT_KEYS;
+    if (n_sh == 0 || S == 1 || a.nk <= LM_SPLIT_KEYS) return launch_lm_attention(out_t, a0, B, hq, s);
+    const int n_chunks = (int)ceil_div(S, items);
+    const int n_shared_wg = n_sh * a.hkv * (B / S) * n_chunks;
+    const dim3 grid(n_shared_wg + (a.n_split - n_sh) * a.hkv * B);
+#define ACEMI_LM_ATTN_SHARED(I, R)                                                                                \
+    if (items == I && rep == R)                                                                                    \
+    hipLaunchKernelGGL((lm_attn_shared_kernel<I, R>), grid, dim3(256), 0, s, a, n_sh, n_chunks, n_shared_wg)
+    ACEMI_LM_ATTN_SHARED(2, 1);
+    ACEMI_LM_ATTN_SHARED(4, 1);
+    ACEMI_LM_ATTN_SHARED(8, 1);
+    ACEMI_LM_ATTN_SHARED(2, 2);
+    ACEMI_LM_ATTN_SHARED(4, 2);
+    ACEMI_LM_ATTN_SHARED(8, 2);
+    ACEMI_LM_ATTN_SHARED(2, 4);
+    ACEMI_LM_ATTN_SHARED(4, 4);
+#undef ACEMI_LM_ATTN_SHARED
+    ACEMI_HIP(hipGetLastError());
+    lm_attn_merge(out_t == ActType::F16, a, B, hq, s);
+}
+
+void launch_lm_attention(ActType out_t, const LmAttnArgs& a0, int B, int hq, hipStream_t s) {
+    LmAttnArgs a = a0;
+    const int rep = lm_attn_check(a, B, hq);
     const dim3 grid(a.n_split, a.hkv, B);
     const bool f16 = out_t == ActType::F16;
 #define ACEMI_LM_ATTN(R)                                                                  \
@@ -436,13 +541,7 @@ void launch_lm_attention(ActType out_t, const LmAttnArgs& a0, int B, int hq, hip
     }
 #undef ACEMI_LM_ATTN
     ACEMI_HIP(hipGetLastError());
-    if (a.n_split > 1) {
-        if (f16)
-            hipLaunchKernelGGL(lm_attn_merge_kernel<true>, dim3(hq, B), dim3(128), 0, s, a.part, hq, a.n_split, a.out);
-        else
-            hipLaunchKernelGGL(lm_attn_merge_kernel<false>, dim3(hq, B), dim3(128), 0, s, a.part, hq, a.n_split, a.out);
-        ACEMI_HIP(hipGetLastError());
-    }
+    if (a.n_split > 1) lm_attn_merge(f16, a, B, hq, s);
 }
 
 }  // namespace acemi

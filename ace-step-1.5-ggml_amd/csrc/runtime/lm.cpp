@@ -18,6 +18,7 @@
 #include <random>
 #include <vector>
 
+#include "../kernels/lm_attn_shared_host.h"  // empty under hipcc; the host build's launch_lm_attention_shared
 #include "../kernels/lm_decode_q_host.h"  // empty under hipcc; the host build's launch_lm_skinny_q / launch_lm_embed_q
 #include "../kernels/lm_fanout_host.h"    // empty under hipcc; the host build's launch_lm_cache_fanout
 #include "../kernels/lm_sample_host.h"    // empty under hipcc; the host build's launch_lm_select
@@ -42,7 +43,11 @@ class LmEngine {
     int capacity() const { return capacity_; }
     int len() const { return len_; }
     size_t cache_bytes() const { return kc_.bytes + vc_.bytes + kmask_.bytes; }
-    void reset() { len_ = 0; }
+    void reset() {
+        len_ = 0;
+        shared_len_ = 0;
+        shared_group_ = 1;
+    }
 
     // bytes per position and sequence: K and V, fp16, every layer
     size_t token_bytes() const {
@@ -82,7 +87,7 @@ class LmEngine {
         part_.ensure(lm_attn_part_floats(B, c.hq, cap) * 4);
         batch_ = B;
         capacity_ = cap;
-        len_ = 0;
+        reset();
     }
 
     // The cache of batch_ = G sequences re-laid for G * copies sequences of `cap` positions (kernels/lm_fanout.hip):
@@ -126,6 +131,14 @@ class LmEngine {
         kmask_ = std::move(mn);
         batch_ = B;
         capacity_ = cap;
+        if (copies > 1) {  // ACE_MI_LM_SHARED_PREFIX=1: decode attention reads the copied positions once per group
+            const char* e = std::getenv("ACE_MI_LM_SHARED_PREFIX");
+            const bool on = e && std::atoi(e) != 0;
+            shared_len_ = on ? len_ : 0;
+            shared_group_ = on ? copies : 1;
+            e = std::getenv("ACE_MI_LM_SHARED_ITEMS");  // measuring: items per shared workgroup, 2 / 4 / 8
+            shared_items_ = e ? std::atoi(e) : 0;
+        }
     }
 
     // the caller has checked batch, capacity and the prefill rule
@@ -330,6 +343,8 @@ class LmEngine {
         const TextConfig& c = model_.cfg;
         const BlockShape sh = shape();
         const int M = batch_ * n;
+        shared_len_ = 0;  // a prefill starts from an empty cache: nothing in it is a copy
+        shared_group_ = 1;
         float* x = blocks_.x(M, sh.hidden);
         embed(d_ids, M, x, s);
         const BlockRunner::AfterQkv fill = [&](int li, float* qkv, int ld) {
@@ -368,7 +383,14 @@ class LmEngine {
             aa.scale = 1.0f / std::sqrt((float)D);
             aa.out = attn;
             aa.part = part_.as<float>();
-            launch_lm_attention(at, aa, B, c.hq, s);
+            if (shared_group_ > 1) {
+                aa.n_shared = shared_len_;
+                aa.group_size = shared_group_;
+                aa.shared_items = shared_items_;
+                launch_lm_attention_shared(at, aa, B, c.hq, s);
+            } else {
+                launch_lm_attention(at, aa, B, c.hq, s);
+            }
             skinny(at, attn, qd, ly.w_o, H, qd, LM_EPI_RESID, x, nullptr, H, s);
             launch_rmsnorm_mod(at, x, B, H, ly.mlp_norm, nullptr, nullptr, 0, 1, c.eps, act, s);
             skinny(at, act, H, ly.w_gu, 2 * I, H, LM_EPI_SWIGLU, nullptr, act2, I, s);
@@ -384,6 +406,10 @@ class LmEngine {
     DevBuf sel_work_, sel_next_, sel_done_, sel_uni_;  // selection scratch, the next step's ids, the stop words, uniforms
     RopeTable rope_;  // positions 0..capacity-1
     int batch_ = 0, capacity_ = 0, len_ = 0;
+    // Set by fanout(copies > 1), cleared by begin, reset and prefill: sequences g * shared_group_ + s hold sequence
+    // g * shared_group_'s K, V and mask rows bit for bit at positions [0, shared_len_), launch_lm_attention_shared's
+    // precondition.  It holds for the life of the loop: a decode step only appends at pos = len_ >= shared_len_.
+    int shared_len_ = 0, shared_group_ = 1, shared_items_ = 0;
 };
 
 }  // namespace acemi

@@ -335,15 +335,19 @@ ace_ggml_status ace_mi_kernel_lm_cache_fanout(int32_t layers, int32_t G, int32_t
     return ACE_GGML_OK;
 }
 
-ace_ggml_status ace_mi_kernel_lm_attention(int32_t out_type, int32_t B, int32_t hq, int32_t hkv, int32_t capacity,
-                                           int32_t nk, float scale, const float* q, const uint16_t* k_cache,
-                                           const uint16_t* v_cache, const int32_t* key_mask, uint16_t* out_u16) {
+namespace {
+// both attention entries: group_size 0 = launch_lm_attention, else launch_lm_attention_shared
+ace_ggml_status lm_attention_entry(const char* name, int32_t out_type, int32_t B, int32_t group_size, int32_t n_shared,
+                                   int32_t hq, int32_t hkv, int32_t capacity, int32_t nk, float scale, const float* q,
+                                   const uint16_t* k_cache, const uint16_t* v_cache, const int32_t* key_mask,
+                                   uint16_t* out_u16) {
     using namespace acemi;
     if ((out_type != 0 && out_type != 1) || B < 1 || B > LM_MAX_BATCH || hkv < 1 || hq < 1 || hq % hkv != 0 || nk < 1 ||
         nk > capacity || !q || !k_cache || !v_cache || !key_mask || !out_u16)
         return ACE_GGML_ERR_INVALID_ARG;
     const int rep = hq / hkv;
     if (rep != 1 && rep != 2 && rep != 4) return ACE_GGML_ERR_INVALID_ARG;
+    if (group_size && (B % group_size != 0 || n_shared < 0 || n_shared > nk - 1)) return ACE_GGML_ERR_INVALID_ARG;
     try {
         const size_t nc = (size_t)B * hkv * capacity * D * 2, no = (size_t)B * hq * D * 2;
         DevMem dq(q, (size_t)B * hq * D * 4), dk(k_cache, nc), dv(v_cache, nc), dm(key_mask, (size_t)B * capacity * 4);
@@ -359,14 +363,36 @@ ace_ggml_status ace_mi_kernel_lm_attention(int32_t out_type, int32_t B, int32_t 
         a.scale = scale;
         a.out = dout.as<uint16_t>();
         a.part = dpart.as<float>();
-        launch_lm_attention(out_type == 1 ? ActType::F16 : ActType::BF16, a, B, hq, nullptr);
+        a.n_shared = n_shared;
+        a.group_size = group_size ? group_size : 1;
+        if (group_size)
+            launch_lm_attention_shared(out_type == 1 ? ActType::F16 : ActType::BF16, a, B, hq, nullptr);
+        else
+            launch_lm_attention(out_type == 1 ? ActType::F16 : ActType::BF16, a, B, hq, nullptr);
         ACEMI_HIP(hipDeviceSynchronize());
         dout.to_host(out_u16, no);
     } catch (const std::exception& ex) {
-        std::fprintf(stderr, "ace_mi_kernel_lm_attention: %s\n", ex.what());
+        std::fprintf(stderr, "%s: %s\n", name, ex.what());
         return ACE_GGML_ERR;
     }
     return ACE_GGML_OK;
+}
+}  // namespace
+
+ace_ggml_status ace_mi_kernel_lm_attention(int32_t out_type, int32_t B, int32_t hq, int32_t hkv, int32_t capacity,
+                                           int32_t nk, float scale, const float* q, const uint16_t* k_cache,
+                                           const uint16_t* v_cache, const int32_t* key_mask, uint16_t* out_u16) {
+    return lm_attention_entry("ace_mi_kernel_lm_attention", out_type, B, 0, 0, hq, hkv, capacity, nk, scale, q, k_cache,
+                              v_cache, key_mask, out_u16);
+}
+
+ace_ggml_status ace_mi_kernel_lm_attention_shared(int32_t out_type, int32_t G, int32_t S, int32_t hq, int32_t hkv,
+                                                  int32_t capacity, int32_t nk, int32_t n_shared, float scale,
+                                                  const float* q, const uint16_t* k_cache, const uint16_t* v_cache,
+                                                  const int32_t* key_mask, uint16_t* out_u16) {
+    if (G < 1 || S < 1 || G > acemi::LM_MAX_BATCH || S > acemi::LM_MAX_BATCH) return ACE_GGML_ERR_INVALID_ARG;
+    return lm_attention_entry("ace_mi_kernel_lm_attention_shared", out_type, G * S, S, n_shared, hq, hkv, capacity, nk,
+                              scale, q, k_cache, v_cache, key_mask, out_u16);
 }
 
 }  // extern "C"

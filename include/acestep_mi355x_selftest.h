@@ -198,6 +198,15 @@ ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_attention(int32_t out_type, int32_
                                                         int32_t capacity, int32_t nk, float scale, const float* q,
                                                         const uint16_t* k_cache, const uint16_t* v_cache,
                                                         const int32_t* key_mask, uint16_t* out_u16);
+/* The same over a cache of G groups of S sequences (B = G * S) in which sequence g * S + s holds sequence g * S's K, V
+ * and key_mask rows bit for bit at positions [0, n_shared) (launch_lm_attention_shared): the output equals
+ * ace_mi_kernel_lm_attention's on the same arrays bit for bit.  ACE_GGML_ERR_INVALID_ARG for what the launcher refuses:
+ * G or S < 1, G * S > 8, n_shared < 0 or > nk - 1, a GQA ratio other than 1, 2, 4. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_attention_shared(int32_t out_type, int32_t G, int32_t S, int32_t hq,
+                                                               int32_t hkv, int32_t capacity, int32_t nk,
+                                                               int32_t n_shared, float scale, const float* q,
+                                                               const uint16_t* k_cache, const uint16_t* v_cache,
+                                                               const int32_t* key_mask, uint16_t* out_u16);
 /* Token selection (kernels/lm_sample.hip; semantics: ace_mi_lm_select in acestep_mi355x.h) on host arrays with padded
  * leading dimensions: logits [B][ld_logits] (S = B, or B / 2 when cfg_scale > 1), allowed [n_allowed] or NULL, uniform
  * [S] or NULL, seen [S][ld_seen] bytes or NULL (in-out), tokens [S * token_stride] (in-out: word s * token_stride is

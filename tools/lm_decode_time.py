@@ -24,9 +24,14 @@ on the block planes, 1.125 / 0.75 / 1.25 bytes per weight); torch eager is measu
   (c) ace_mi_lm_generate: --calls calls of --steps tokens each, the call's wall time / tokens (the prefill is outside);
   and the selection kernel alone (ace_mi_lm_select).  (a), (b) and the kernel are timed per token with event pairs.
 
+--fanout 2x4,1x8 measures the B = G * S decode step of the batched codes loop: a --prompt token prefill of G sequences,
+ace_mi_lm_fanout to G * S, then steps; ACE_MI_LM_SHARED_PREFIX = 0 (lm_attn_kernel per sequence) and 1
+(lm_attn_shared_kernel) alternate --rounds times in one process, --items 2,4 adds forced items per workgroup.
+
   python tools/lm_decode_time.py --models 0.6b,1.7b --steps 30 --warmup 5 [--gguf Q8_0,Q4_K,Q6_K] [--no-torch]
                                  [--json out.json]
-  python tools/lm_decode_time.py --generate --models 0.6b,1.7b --steps 30 --warmup 5 [--calls 5] [--json out.json]"""
+  python tools/lm_decode_time.py --generate --models 0.6b,1.7b --steps 30 --warmup 5 [--calls 5] [--json out.json]
+  python tools/lm_decode_time.py --fanout 2x4,1x8 --models 0.6b,1.7b --steps 30 --warmup 5 [--items 2,4] [--json out.json]"""
 import argparse
 import json
 import os
@@ -167,6 +172,58 @@ def generate_times(ckpt, cfg, warm, steps, calls, cache=1024, n_codes=64000):
     return rows
 
 
+def fanout_times(ckpt, cfg, groups, prompt, warm, steps, rounds, modes):
+    """{(G, S, mode): times} of the decode step after ace_mi_lm_fanout: a `prompt`-token prefill of G sequences fanned
+    out to G * S.  mode = (ACE_MI_LM_SHARED_PREFIX, ACE_MI_LM_SHARED_ITEMS); the fan-out reads both on each call, so
+    the modes alternate inside one process, `rounds` times, each round from a fresh prefill."""
+    import torch
+    from acestep_mi355x.capi import GGMLCAPIBridge
+    br = GGMLCAPIBridge()
+    br.load_lm(ckpt)
+    g = torch.Generator().manual_seed(0)
+    ms = {}
+    for G, S in groups:
+        ids = torch.randint(0, cfg["vocab_size"], (G, prompt), generator=g, dtype=torch.int32).cuda()
+        tok = ids[:1, :1].repeat(G * S, 1).contiguous()
+        for _ in range(rounds):
+            for mode in modes:
+                os.environ["ACE_MI_LM_SHARED_PREFIX"], os.environ["ACE_MI_LM_SHARED_ITEMS"] = mode
+                br.lm_begin(G, prompt)
+                br.lm_fanout(S, prompt + warm + steps, br.lm_forward(ids))
+                t = time_steps(lambda: br.lm_forward(tok), warm, steps)
+                ms.setdefault((G, S, mode), []).append(t)
+    br.close()
+    return {k: dict(median=statistics.median(t["median"] for t in v), min=min(t["min"] for t in v),
+                    max=max(t["max"] for t in v), round_medians=[t["median"] for t in v]) for k, v in ms.items()}
+
+
+def main_fanout(a):
+    """--fanout: the B = G * S decode step behind a shared prompt, shared-prefix attention off and on, interleaved"""
+    groups = [tuple(int(x) for x in gs.split("x")) for gs in a.fanout.split(",")]
+    modes = [("0", "0"), ("1", "0")] + [("1", i) for i in a.items.split(",") if i]
+    print("| model | G x S | prompt | ACE_MI_LM_SHARED_PREFIX | items / workgroup | ms/step median of rounds (min-max of steps) "
+          "| round medians |")
+    print("|---|---|---|---|---|---|---|")
+    out = []
+    for name in a.models.split(","):
+        cfg = dict(SHAPES[name], vocab_size=a.vocab)
+        with tempfile.TemporaryDirectory(prefix="acemi_lmtime_") as tmp:
+            d = os.path.join(a.ckpt_dir or tmp, name)      # --ckpt-dir: written once, read by later runs (another library)
+            if not os.path.exists(os.path.join(d, "config.json")):
+                os.makedirs(d, exist_ok=True)
+                _write(d, cfg)
+            res = fanout_times(d, cfg, groups, a.prompt, a.warmup, a.steps, a.rounds, modes)
+        for (G, S, mode), t in res.items():
+            out.append(dict(model=name, G=G, S=S, prompt=a.prompt, shared_prefix=mode[0], items=mode[1], ms=t))
+            print(f"| {name} | {G} x {S} | {a.prompt} | {mode[0]} | {mode[1] if mode[1] != '0' else 'rule'} | "
+                  f"{t['median']:.3f} ({t['min']:.3f}-{t['max']:.3f}) | "
+                  f"{' '.join('%.3f' % m for m in t['round_medians'])} |", flush=True)
+    if a.json:
+        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
+        with open(a.json, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def torch_times(ckpt, cfg, Bs, lens, warm, steps):
     import torch
     from safetensors.torch import load_file
@@ -213,9 +270,16 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--generate", action="store_true", help="time the audio-code phase: step, per-token torch path, engine loop")
     ap.add_argument("--calls", type=int, default=5)
+    ap.add_argument("--fanout", default="", help="GxS[,GxS]: time the step after ace_mi_lm_fanout, shared-prefix attention off / on")
+    ap.add_argument("--prompt", type=int, default=1024, help="--fanout: tokens of the shared prompt")
+    ap.add_argument("--rounds", type=int, default=5, help="--fanout: alternations of the modes")
+    ap.add_argument("--ckpt-dir", default=None, help="--fanout: keep the synthetic checkpoints here between runs")
+    ap.add_argument("--items", default="", help="--fanout: also time these ACE_MI_LM_SHARED_ITEMS values (2, 4, 8)")
     a = ap.parse_args()
     if a.generate:
         return main_generate(a)
+    if a.fanout:
+        return main_fanout(a)
     Bs, lens = [int(x) for x in a.batch.split(",")], [int(x) for x in a.cache.split(",")]
     rows = []
     print("| model | B | cache | engine ms/step median (min-max) | bytes/step MB (weights + cache) | bytes / 8.0 TB/s ms "
