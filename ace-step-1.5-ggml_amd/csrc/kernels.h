@@ -141,72 +141,80 @@ struct DequantBlocksJob {
 // any number of jobs: grouped by type, up to 8 jobs per launch; jobs of one call must not write the same rows
 void launch_dequant_blocks(const DequantBlocksJob* jobs, int n, hipStream_t s);
 
-// ------------------------------------------------- LoRA merge (kernels/lora.hip)
-// The adapted 16-bit image of a (possibly fused) weight matrix: for module row o and column i
-//   acc = 0; for j = 0 .. r-1 ascending: acc = acc + B[o][j] * A[j][i]   (multiply and add each rounded to f32,
-//   never contracted);  t = eff * acc;  out = rne16(f32(base) + t)  in the matrix's own 16-bit format,
-// so numpy restates it bit for bit (acestep_mi355x/synthetic.py lora_delta_bits).  A job covers the fused rows
-// [row0, row0 + rows) of base / out; the row map places module row o at a fused row inside that range, and the
-// rows of the range that the map does not reach are copied from base when copy_rest is set (left untouched
+// ------------------------------------------------- adapter merges (kernels/lora.hip, kernels/lokr.hip)
+// Both merges write the adapted 16-bit image of a (possibly fused) weight matrix, out = rne16(f32(base) + t) in the
+// matrix's own 16-bit format, where t is the kind's delta (below).  A MergeTarget says which rows of which image: the
+// fused rows [row0, row0 + rows) of base / out; the row map places module row o at a fused row inside that range,
+// and the rows of the range that the map does not reach are copied from base when copy_rest is set (left untouched
 // otherwise).  out == base (in place) is allowed; columns >= cols of a row and rows outside the range are never
-// written.  cols, ld_base, ld_out % 8 == 0 and 16-byte aligned base / out / A (16-byte accesses on the matrix).
+// written.  cols, ld_base, ld_out % 8 == 0 and 16-byte aligned base / out (16-byte accesses on the matrix).
 enum LoraRowMap : int {
     LORA_ROWS_PLAIN = 0,       // fused row = row_off + o (row_off: the module's offset inside a q|k|v or k|v concatenation)
     LORA_ROWS_INTERLEAVE = 1,  // w_gu: fused row = (o / 16) * 32 + half * 16 + o % 16 (half 0 = gate, 1 = up)
 };
-struct LoraMergeJob {
+struct MergeTarget {
     int fmt = WF_BF16;  // WF_BF16 | WF_F16, of base and out
     const uint16_t* base = nullptr;
     int64_t ld_base = 0;
     uint16_t* out = nullptr;
     int64_t ld_out = 0;
     int row0 = 0, rows = 0, cols = 0;
-    const float* A = nullptr;  // [r][cols]; null (r = 0): no module, the whole range is copy-through
-    const float* B = nullptr;  // [rows_mod][r]
-    int r = 0, rows_mod = 0;
-    float eff = 0.f;
     int map = LORA_ROWS_PLAIN;
     int row_off = 0;  // LORA_ROWS_PLAIN
     int half = 0;     // LORA_ROWS_INTERLEAVE
     bool copy_rest = false;
 };
-constexpr int LORA_MAX_RANK = 128;
-// module row of fused row fr, or -1 when fr belongs to no row of the job's module
-__host__ __device__ inline int lora_module_row(int map, int row_off, int half, int rows_mod, int r, int fr) {
-    if (r <= 0) return -1;
+// module row of fused row fr, or -1 when fr belongs to no row of a module of rows_mod rows (0: no module)
+__host__ __device__ inline int merge_module_row(const MergeTarget& t, int rows_mod, int fr) {
     int o;
-    if (map == LORA_ROWS_INTERLEAVE) {
-        if (((fr >> 4) & 1) != half) return -1;
+    if (t.map == LORA_ROWS_INTERLEAVE) {
+        if (((fr >> 4) & 1) != t.half) return -1;
         o = (fr >> 5) * 16 + (fr & 15);
     } else {
-        o = fr - row_off;
+        o = fr - t.row_off;
     }
     return (o >= 0 && o < rows_mod) ? o : -1;
 }
-// fused row of module row o (the inverse of lora_module_row)
-__host__ __device__ inline int lora_fused_row(int map, int row_off, int half, int o) {
-    return map == LORA_ROWS_INTERLEAVE ? (o >> 4) * 32 + half * 16 + (o & 15) : row_off + o;
+// fused row of module row o (the inverse of merge_module_row)
+__host__ __device__ inline int merge_fused_row(const MergeTarget& t, int o) {
+    return t.map == LORA_ROWS_INTERLEAVE ? (o >> 4) * 32 + t.half * 16 + (o & 15) : t.row_off + o;
 }
+// what every merge launcher (kernel or host loop) requires of a target; `who` prefixes the message
+inline void check_merge_target(const MergeTarget& t, const char* who) {
+    const std::string w(who);
+    ACEMI_CHECK((t.fmt == WF_BF16 || t.fmt == WF_F16) && t.base && t.out, w + ": dense 16-bit matrices");
+    ACEMI_CHECK(t.rows > 0 && t.row0 >= 0 && t.cols > 0 && t.cols % 8 == 0 && t.ld_base % 8 == 0 && t.ld_out % 8 == 0 &&
+                    t.ld_base >= t.cols && t.ld_out >= t.cols,
+                w + ": cols and leading dimensions must be multiples of 8");
+    ACEMI_CHECK(((uintptr_t)t.base | (uintptr_t)t.out) % 16 == 0, w + ": 16-byte aligned base / out");
+    ACEMI_CHECK(t.map == LORA_ROWS_PLAIN || (t.map == LORA_ROWS_INTERLEAVE && (t.half == 0 || t.half == 1)),
+                w + ": bad row map");
+}
+
+// LoRA (kernels/lora.hip): for module row o and column i
+//   acc = 0; for j = 0 .. r-1 ascending: acc = acc + B[o][j] * A[j][i]   (multiply and add each rounded to f32,
+//   never contracted);  t = eff * acc,
+// so numpy restates it bit for bit (acestep_mi355x/synthetic.py lora_delta_bits).  A is 16-byte aligned.
+struct LoraMergeJob {
+    MergeTarget t;
+    const float* A = nullptr;  // [r][cols]; null (r = 0): no module, the whole range is copy-through
+    const float* B = nullptr;  // [rows_mod][r]
+    int r = 0, rows_mod = 0;
+    float eff = 0.f;
+};
+constexpr int LORA_MAX_RANK = 128;
 // any number of jobs (launches of up to 8 jobs each); jobs of one call must not write the same rows
 void launch_lora_merge(const LoraMergeJob* jobs, int n, hipStream_t s);
 
-// ------------------------------------------------- LoKr merge (kernels/lokr.hip)
-// The adapted 16-bit image for a LyCORIS LoKr module of a*c rows and b*d (= cols) columns: the delta is the
-// Kronecker product  dW[i*c + k][j*d + l] = w1[i][j] * W2[k][l]  and
-//   v = w1[i][j] * W2[k][l];  t = eff * v;  out = rne16(f32(base) + t)   (each operation rounded to f32 on its own),
+// LoKr (kernels/lokr.hip): a LyCORIS module of a*c rows and b*d (= cols) columns, whose delta is the Kronecker product
+//   v = w1[i][j] * W2[k][l];  t = eff * v  at row i*c + k, column j*d + l   (each operation rounded to f32 on its own),
 // where w1 [a][b] is stored (w1) or the product w1a [a][r1] . w1b [r1][b], and W2 [c][d] is stored (w2) or
 // w2a [c][r2] . w2b [r2][d]; a product entry is the chain  acc = 0; for j ascending: acc = acc + L[m][j] * R[j][n]
-// of LoraMergeJob (never contracted), so numpy restates all of it bit for bit (acestep_mi355x/synthetic.py
-// lokr_delta).  Rows, row maps, copy-through rows, in place and alignment are LoraMergeJob's.  A job whose factor
-// is a product needs the f32 workspace ws of lokr_ws_floats() floats, which launch_lokr_merge fills (the products,
-// once per job) before the merge reads it; jobs of one call must not share a workspace.
+// of LoRA (never contracted), so numpy restates all of it bit for bit (acestep_mi355x/synthetic.py lokr_delta).
+// A job whose factor is a product needs the f32 workspace ws of lokr_ws_floats() floats, which launch_lokr_merge
+// fills (the products, once per job) before the merge reads it; jobs of one call must not share a workspace.
 struct LokrMergeJob {
-    int fmt = WF_BF16;  // WF_BF16 | WF_F16, of base and out
-    const uint16_t* base = nullptr;
-    int64_t ld_base = 0;
-    uint16_t* out = nullptr;
-    int64_t ld_out = 0;
-    int row0 = 0, rows = 0, cols = 0;
+    MergeTarget t;
     int a = 0, b = 0, c = 0, d = 0;  // a = 0: no module, the whole range is copy-through
     const float* w1 = nullptr;   // [a][b], or null with
     const float* w1a = nullptr;  // [a][r1]
@@ -218,10 +226,6 @@ struct LokrMergeJob {
     int r2 = 0;
     float* ws = nullptr;
     float eff = 0.f;
-    int map = LORA_ROWS_PLAIN;
-    int row_off = 0;
-    int half = 0;
-    bool copy_rest = false;
 };
 constexpr int LOKR_MAX_RANK = 1024;
 // floats of a job's workspace: W2 [c][d] when it is a product (rounded up to 4), then w1 [a][b] when it is one

@@ -1,7 +1,7 @@
 // LoKr merge (gfx950): the adapted 16-bit image of a weight matrix under a LyCORIS Kronecker adapter,
 // out[i*c + k][j*d + l] = rne16(f32(base) + eff * (w1[i][j] * W2[k][l])), with the fixed arithmetic of kernels.h
 // (LokrMergeJob): every multiply and add rounded to f32 on its own, low-rank factors as rank-ordered chains, so every
-// build of it (these kernels, the host loops of runtime/engine.cpp, numpy) gives the same bits.
+// build of it (these kernels, the host loops of kernels/merge_host.h, numpy) gives the same bits.
 //
 // Two kernels per batch of up to 8 jobs:
 //   lokr_factor_kernel  forms the factors that are stored as products (W2 = w2a . w2b, w1 = w1a . w1b) once per job
@@ -18,12 +18,11 @@
 //       columns that straddle a j boundary (d % 8 != 0) and rows that cross an i boundary index per element; one
 //       16-byte load and one 16-byte store per row.  Per element: two LDS reads, two multiplies, one add.
 // Copy-through rows of a fused matrix (a module without an adapter) are moved by tiles of the same shape that only
-// load and store, through the row maps of LoraMergeJob.
+// load and store; the batch, the tile walk and that tile are merge_common.h's.
 #include <algorithm>
 #include <climits>
 
-#include "../kernels.h"
-#include "merge16.h"
+#include "merge_common.h"
 
 // the chain is never contracted into FMAs (the kernel files build with -ffp-contract=fast-honor-pragmas)
 #pragma clang fp contract(off)
@@ -31,9 +30,9 @@
 namespace acemi {
 namespace {
 
-constexpr int TR = 32;    // module rows per merge tile
-constexpr int TC = 256;   // columns per merge tile
 constexpr int RPT = 4;    // rows per thread (8 row groups x 32 column groups of 8)
+constexpr int TR = 8 * RPT;   // module rows per merge tile
+constexpr int TC = MERGE_TC;  // columns per merge tile
 constexpr int FR = 16;    // rows per factor tile
 constexpr int FC = 64;    // columns per factor tile
 constexpr int RC = 32;    // ranks per LDS chunk
@@ -52,22 +51,14 @@ struct LokrFactorBatch {
 };
 
 struct LokrTileJob {  // a LokrMergeJob with its factors resolved to whole matrices
-    const uint16_t* base;
-    uint16_t* out;
-    int64_t ld_base, ld_out;
+    MergeTarget t;
     const float* w1;  // [a][b]
     const float* W2;  // [c][d]
-    int fmt, row0, rows, cols, rows_mod;  // rows_mod = a * c; 0: copy-only
+    int rows_mod;     // a * c; 0: copy-only
     int a, b, c, d;
     float eff;
-    int map, row_off, half;
 };
-struct LokrBatch {
-    LokrTileJob job[8];
-    int mod_tiles[8];  // tiles of module rows of job i
-    int end[8];        // exclusive prefix sums of (module + copy) tiles
-    int n;
-};
+using LokrBatch = MergeBatch<RPT, LokrTileJob>;
 
 __global__ void __launch_bounds__(256) lokr_factor_kernel(LokrFactorBatch b) {
     __shared__ __attribute__((aligned(16))) float Rs[RC][FC];
@@ -140,39 +131,24 @@ inline int lokr_span(int tile, int f, int count) {  // blocks of width f a tile-
 __global__ void __launch_bounds__(256) lokr_merge_kernel(LokrBatch b) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
 
-    int ji = 0;
-#pragma unroll
-    for (int i = 0; i < 7; ++i) ji += (i + 1 < b.n && (int)blockIdx.x >= b.end[i]) ? 1 : 0;
-    const LokrTileJob& jb = b.job[ji];
-    int tile = (int)blockIdx.x - (ji > 0 ? b.end[ji - 1] : 0);
-    const int col_tiles = (jb.cols + TC - 1) / TC;
-    const bool copy_tile = tile >= b.mod_tiles[ji];
-    if (copy_tile) tile -= b.mod_tiles[ji];
-    const int c0 = (tile % col_tiles) * TC;
-    const int r0 = (tile / col_tiles) * TR;  // first module row (merge tile) / first row of the range (copy tile)
+    const MergeTile mt = merge_tile(b, (int)blockIdx.x);
+    // by value: the job's fields are fetched from the kernel argument once, here, instead of again inside every row's
+    // branch (the compiler does not hoist a scalar load out of a conditional block)
+    const LokrTileJob jb = b.job[mt.ji];
+    const MergeTarget& tg = jb.t;
+    const int c0 = mt.c0, r0 = mt.r0;
 
     const int tid = threadIdx.x;
     const int cg = tid & 31, rg = tid >> 5;
     const int col = c0 + cg * 8;
-    const bool col_ok = col < jb.cols;  // cols % 8 == 0: a thread's 8 columns are all inside or all outside
-    const int row_end = jb.row0 + jb.rows;
+    const bool col_ok = col < tg.cols;  // cols % 8 == 0: a thread's 8 columns are all inside or all outside
+    const int row_end = tg.row0 + tg.rows;
 
-    if (copy_tile) {  // rows of the range that belong to no module row: base -> out
-#pragma unroll
-        for (int k = 0; k < RPT; ++k) {
-            const int fr = jb.row0 + r0 + rg * RPT + k;
-            if (fr < row_end && col_ok &&
-                lora_module_row(jb.map, jb.row_off, jb.half, jb.rows_mod, jb.rows_mod, fr) < 0) {
-                const uint4 v = *reinterpret_cast<const uint4*>(jb.base + (int64_t)fr * jb.ld_base + col);
-                *reinterpret_cast<uint4*>(jb.out + (int64_t)fr * jb.ld_out + col) = v;
-            }
-        }
-        return;
-    }
+    if (mt.copy_tile) return merge_copy_tile<RPT>(tg, jb.rows_mod, r0, rg, col);
 
     const int c = jb.c, d = jb.d;
     const int nk = lokr_nk(c), nl = lokr_nl(d);
-    const int rows_in = min(TR, jb.rows_mod - r0), cols_in = min(TC, jb.cols - c0);
+    const int rows_in = min(TR, jb.rows_mod - r0), cols_in = min(TC, tg.cols - c0);
     const int i0 = r0 / c, j0 = c0 / d;
     const int ni = (r0 + rows_in - 1) / c - i0 + 1, nj = (c0 + cols_in - 1) / d - j0 + 1;
     const int nlw = lokr_row_words(nl);
@@ -202,7 +178,7 @@ __global__ void __launch_bounds__(256) lokr_merge_kernel(LokrBatch b) {
             if (++l == d) l = 0, ++j;
         }
     }
-    const bool f16 = jb.fmt == WF_F16;
+    const bool f16 = tg.fmt == WF_F16;
     const float eff = jb.eff;
     int o = r0 + rg * RPT;
     int i = o / c, k = o - i * c;
@@ -212,9 +188,9 @@ __global__ void __launch_bounds__(256) lokr_merge_kernel(LokrBatch b) {
         const float* w2r = W2s + (c <= TR ? k : o - r0) * nlw;
         const float* w1r = w1s + (i - i0) * nj;
         if (++k == c) k = 0, ++i;
-        const int fr = lora_fused_row(jb.map, jb.row_off, jb.half, o);
-        if (fr < jb.row0 || fr >= row_end) continue;
-        const uint4 w = *reinterpret_cast<const uint4*>(jb.base + (int64_t)fr * jb.ld_base + col);
+        const int fr = merge_fused_row(tg, o);
+        if (fr < tg.row0 || fr >= row_end) continue;
+        const uint4 w = *reinterpret_cast<const uint4*>(tg.base + (int64_t)fr * tg.ld_base + col);
         const uint32_t wi[4] = {w.x, w.y, w.z, w.w};
         uint32_t oi[4];
 #pragma unroll
@@ -226,7 +202,7 @@ __global__ void __launch_bounds__(256) lokr_merge_kernel(LokrBatch b) {
             const float s1 = f16_to_f32(f16, (uint16_t)(wi[e / 2] >> 16)) + t1;
             oi[e / 2] = (uint32_t)f32_to_16(f16, s0) | ((uint32_t)f32_to_16(f16, s1) << 16);
         }
-        *reinterpret_cast<uint4*>(jb.out + (int64_t)fr * jb.ld_out + col) = make_uint4(oi[0], oi[1], oi[2], oi[3]);
+        *reinterpret_cast<uint4*>(tg.out + (int64_t)fr * tg.ld_out + col) = make_uint4(oi[0], oi[1], oi[2], oi[3]);
     }
 }
 
@@ -238,28 +214,21 @@ void launch_lokr_merge(const LokrMergeJob* jobs, int n, hipStream_t s) {
         LokrBatch b{};
         LokrFactorBatch fb{};
         int tot = 0, ftot = 0, lds_floats = 0;
-        b.n = std::min(8, n - j0);
+        const int nb = std::min(8, n - j0);
         auto product = [&](const float* L, const float* R, float* out, int m, int nn, int r) {
             const int tiles = ((m + FR - 1) / FR) * ((nn + FC - 1) / FC);
             fb.p[fb.n] = LokrProduct{L, R, out, m, nn, r};
             ftot += tiles;
             fb.end[fb.n++] = ftot;
         };
-        for (int i = 0; i < b.n; ++i) {
+        for (int i = 0; i < nb; ++i) {
             const LokrMergeJob& jb = jobs[j0 + i];
-            ACEMI_CHECK((jb.fmt == WF_BF16 || jb.fmt == WF_F16) && jb.base && jb.out, "lokr_merge: dense 16-bit matrices");
-            ACEMI_CHECK(jb.rows > 0 && jb.row0 >= 0 && jb.cols > 0 && jb.cols % 8 == 0 && jb.ld_base % 8 == 0 &&
-                            jb.ld_out % 8 == 0 && jb.ld_base >= jb.cols && jb.ld_out >= jb.cols,
-                        "lokr_merge: cols and leading dimensions must be multiples of 8");
-            ACEMI_CHECK(((uintptr_t)jb.base | (uintptr_t)jb.out) % 16 == 0, "lokr_merge: 16-byte aligned base / out");
-            ACEMI_CHECK(jb.map == LORA_ROWS_PLAIN || (jb.map == LORA_ROWS_INTERLEAVE && (jb.half == 0 || jb.half == 1)),
-                        "lokr_merge: bad row map");
+            check_merge_target(jb.t, "lokr_merge");
             LokrTileJob& t = b.job[i];
-            t.base = jb.base, t.out = jb.out, t.ld_base = jb.ld_base, t.ld_out = jb.ld_out;
-            t.fmt = jb.fmt, t.row0 = jb.row0, t.rows = jb.rows, t.cols = jb.cols;
-            t.eff = jb.eff, t.map = jb.map, t.row_off = jb.row_off, t.half = jb.half;
+            t.t = jb.t;
+            t.eff = jb.eff;
             if (jb.a > 0) {
-                ACEMI_CHECK(jb.b > 0 && jb.c > 0 && jb.d > 0 && (int64_t)jb.b * jb.d == jb.cols &&
+                ACEMI_CHECK(jb.b > 0 && jb.c > 0 && jb.d > 0 && (int64_t)jb.b * jb.d == jb.t.cols &&
                                 (int64_t)jb.a * jb.c <= INT_MAX / 2,
                             "lokr_merge: kron([a][b], [c][d]) must have the job's columns");
                 ACEMI_CHECK(jb.w1 || (jb.w1a && jb.w1b && jb.r1 >= 1 && jb.r1 <= LOKR_MAX_RANK),
@@ -281,11 +250,7 @@ void launch_lokr_merge(const LokrMergeJob* jobs, int n, hipStream_t s) {
                 lds_floats = std::max(lds_floats, lokr_nk(jb.c) * lokr_row_words(lokr_nl(jb.d)) +
                                                       lokr_span(TR, jb.c, jb.a) * lokr_span(TC, jb.d, jb.b));
             }
-            const int col_tiles = (jb.cols + TC - 1) / TC;
-            b.mod_tiles[i] = (t.rows_mod + TR - 1) / TR * col_tiles;
-            const bool copies = jb.copy_rest && jb.base != jb.out;  // in place: the copy-through rows are there already
-            tot += b.mod_tiles[i] + (copies ? (jb.rows + TR - 1) / TR * col_tiles : 0);
-            b.end[i] = tot;
+            tot = b.add(t.rows_mod);
         }
         if (tot == 0) continue;
         ACEMI_CHECK(lds_floats * 4 <= 48 * 1024, "lokr_merge: tile LDS");

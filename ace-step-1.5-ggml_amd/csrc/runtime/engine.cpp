@@ -7,13 +7,11 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <tuple>
 #include <type_traits>
 
 #include "../kernels/attn_probs_host.h"  // empty under hipcc; the host build's launch_attn_probs
-#include "lokr.h"
-#include "lora.h"
+#include "../kernels/merge_host.h"       // empty under hipcc; the host build's launch_lora_merge / launch_lokr_merge
+#include "adapter.h"
 #include "operands.h"
 
 namespace acemi {
@@ -42,7 +40,6 @@ DitEngine::~DitEngine() {  // (every DevBuf, and images_, frees itself)
     if (pf_done_) (void)hipEventDestroy(pf_done_);
     if (ev0_) (void)hipEventDestroy(ev0_);
     if (ev1_) (void)hipEventDestroy(ev1_);
-    free_lora();
 }
 
 // Side-stream sweep of the 16-bit images layer li's GEMMs will read (ACE_MI_WEIGHT_PREFETCH), ordered after the work
@@ -547,36 +544,15 @@ void DitEngine::probe_gemm(int which, int M, int iters, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- LoRA adapters (engine.h)
-void DitEngine::free_lora() {
-    images_.adapted.clear();
-    images_.adapter_on = false;
-    lora_ab_.release();
-    lora_a_.clear();
-    lora_b_.clear();
-    lora_.reset();
-    lokr_f_.clear();
-    lokr_ws_off_.clear();
-    lokr_ws_.release();
-    lokr_.reset();
-    lora_scale_ = 0.f;
-    lora_merge_ms_ = 0.0;
-}
-
 DitEngine::LoraInfo DitEngine::lora_info() const {
     LoraInfo i;
-    if (!lora_ && !lokr_) return i;
-    i.loaded = true;
-    i.scale = lora_scale_;
-    i.lora_alpha = lora_ ? lora_->lora_alpha : lokr_->modules[0].alpha;
-    i.min_rank = lora_ ? lora_->min_rank : lokr_->min_rank;
-    i.max_rank = lora_ ? lora_->max_rank : lokr_->max_rank;
-    i.modules = (int)(lora_ ? lora_->modules.size() : lokr_->modules.size());
+    if (!adapter_) return i;
+    adapter_->info(i);
     for (const auto& kv : images_.adapted)
         if (kv.second.p) {
             ++i.images;
             i.image_bytes += kv.second.bytes;
         }
-    i.merge_ms = lora_merge_ms_;
     return i;
 }
 
@@ -588,30 +564,19 @@ void DitEngine::rebuild_lora_images(hipStream_t s) {
     cross_key_.valid = false;
     images_.invalidate();
     images_.adapter_on = false;
-    lora_merge_ms_ = 0.0;
-    if ((!lora_ && !lokr_) || lora_scale_ == 0.f) return;
+    if (!adapter_) return;
+    adapter_->merge_ms = 0.0;
+    if (adapter_->scale == 0.f) return;
 
     const DitModel& m = model_;
     const DitConfig& c = m.cfg;
     const int H = c.hidden, I = c.intermediate, qd = c.hq * c.head_dim, kd = c.hkv * c.head_dim;
-    std::map<std::tuple<int, int, int>, int> index;
-    if (lora_)
-        for (size_t i = 0; i < lora_->modules.size(); ++i) {
-            const LoraModule& lm = lora_->modules[i];
-            index[std::make_tuple(lm.layer, lm.block, lm.proj)] = (int)i;
-        }
-    else
-        for (size_t i = 0; i < lokr_->modules.size(); ++i) {
-            const LokrModule& km = lokr_->modules[i];
-            index[std::make_tuple(km.layer, km.block, km.proj)] = (int)i;
-        }
     struct Slot {  // one module's rows inside a fused matrix
         int map, row_off, half, rows_mod, mod;
     };
     std::vector<std::pair<const DevWeight*, std::vector<Slot>>> mats;
     auto slot = [&](std::vector<Slot>& v, int li, int block, int proj, int map, int row_off, int half, int rows_mod) {
-        const auto it = index.find(std::make_tuple(li, block, proj));
-        v.push_back(Slot{map, row_off, half, rows_mod, it == index.end() ? -1 : it->second});
+        v.push_back(Slot{map, row_off, half, rows_mod, adapter_->find(li, block, proj)});
     };
     const bool ckv_fused = m.w_ckv_all.q != nullptr;
     std::vector<Slot> ckv_all;
@@ -648,8 +613,7 @@ void DitEngine::rebuild_lora_images(hipStream_t s) {
     if (ckv_fused) mats.emplace_back(&m.w_ckv_all, ckv_all);
 
     // allocate first (ensure() synchronises the device), then launch everything in stream order
-    std::vector<LoraMergeJob> jobs;
-    std::vector<LokrMergeJob> kjobs;  // LoKr: the same rows, ranges and maps, the Kronecker factors for A / B
+    adapter_->clear_jobs();
     std::vector<std::pair<const DevWeight*, uint16_t*>> expand;
     for (const auto& mt : mats) {
         const DevWeight& w = *mt.first;
@@ -664,65 +628,36 @@ void DitEngine::rebuild_lora_images(hipStream_t s) {
         if (quantized) expand.emplace_back(&w, img);
         for (size_t k = 0; k < mt.second.size(); ++k) {
             const Slot& sl = mt.second[k];
-            LoraMergeJob j;
-            j.fmt = quantized ? WF_BF16 : w.fmt;
-            j.base = quantized ? img : static_cast<const uint16_t*>(w.q);
-            j.out = img;
-            j.ld_base = j.ld_out = w.cols;
-            j.cols = w.cols;
-            j.map = sl.map;
-            j.row_off = sl.row_off;
-            j.half = sl.half;
+            MergeTarget t;
+            t.fmt = quantized ? WF_BF16 : w.fmt;
+            t.base = quantized ? img : static_cast<const uint16_t*>(w.q);
+            t.out = img;
+            t.ld_base = t.ld_out = w.cols;
+            t.cols = w.cols;
+            t.map = sl.map;
+            t.row_off = sl.row_off;
+            t.half = sl.half;
             if (sl.map == LORA_ROWS_INTERLEAVE) {  // the job's range is the whole matrix; the other half is copied by
-                j.row0 = 0;                        // its own job, or by this one when it has no adapter
-                j.rows = w.rows;
+                t.row0 = 0;                        // its own job, or by this one when it has no adapter
+                t.rows = w.rows;
                 const Slot& other = mt.second[k ^ 1];
-                j.copy_rest = other.mod < 0;
+                t.copy_rest = other.mod < 0;
                 if (sl.mod < 0) continue;
             } else {
-                j.row0 = sl.row_off;
-                j.rows = sl.rows_mod;
-                j.copy_rest = sl.mod < 0;  // a module without an adapter: its rows are copied through
+                t.row0 = sl.row_off;
+                t.rows = sl.rows_mod;
+                t.copy_rest = sl.mod < 0;  // a module without an adapter: its rows are copied through
             }
-            if (lokr_) {
-                if (sl.mod < 0 && quantized) continue;  // in place: the rows are in the image already
-                LokrMergeJob kj;
-                kj.fmt = j.fmt, kj.base = j.base, kj.ld_base = j.ld_base, kj.out = j.out, kj.ld_out = j.ld_out;
-                kj.row0 = j.row0, kj.rows = j.rows, kj.cols = j.cols;
-                kj.map = j.map, kj.row_off = j.row_off, kj.half = j.half, kj.copy_rest = j.copy_rest;
-                if (sl.mod >= 0) {
-                    const LokrModule& km = lokr_->modules[sl.mod];
-                    ACEMI_CHECK(km.in == w.cols && km.out == sl.rows_mod, "lokr: module shape does not match the weight");
-                    const float* const* f = &lokr_f_[6 * (size_t)sl.mod];
-                    kj.a = km.a, kj.b = km.b, kj.c = km.c, kj.d = km.d, kj.r1 = km.r1, kj.r2 = km.r2;
-                    kj.w1 = f[0], kj.w1a = f[1], kj.w1b = f[2], kj.w2 = f[3], kj.w2a = f[4], kj.w2b = f[5];
-                    kj.ws = lokr_ws_.as<float>() + lokr_ws_off_[sl.mod];
-                    kj.eff = lora_scale_ * km.unit;
-                }
-                kjobs.push_back(kj);
-                continue;
-            }
-            if (sl.mod >= 0) {
-                const LoraModule& lm = lora_->modules[sl.mod];
-                ACEMI_CHECK(lm.in == w.cols && lm.out == sl.rows_mod, "lora: module shape does not match the weight");
-                j.A = lora_a_[sl.mod];
-                j.B = lora_b_[sl.mod];
-                j.r = lm.r;
-                j.rows_mod = sl.rows_mod;
-                j.eff = lora_scale_ * lm.unit;
-            } else if (quantized) {
-                continue;  // in place: the rows are in the image already
-            }
-            jobs.push_back(j);
+            if (sl.mod < 0 && quantized) continue;  // in place: the rows are in the image already
+            adapter_->add_job(t, sl.rows_mod, sl.mod);
         }
     }
     ACEMI_HIP(hipDeviceSynchronize());
     const auto t0 = std::chrono::steady_clock::now();
     for (const auto& e : expand) WeightImages::expand(*e.first, e.second, s);
-    launch_lora_merge(jobs.data(), (int)jobs.size(), s);
-    launch_lokr_merge(kjobs.data(), (int)kjobs.size(), s);
+    adapter_->launch(s);
     ACEMI_HIP(hipStreamSynchronize(s));
-    lora_merge_ms_ = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    adapter_->merge_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     images_.adapter_on = true;
 }
 
@@ -730,187 +665,32 @@ void DitEngine::load_lora(const std::string& dir, float scale, int max_layers, h
     if (qact_)
         throw Unsupported("lora: the quantized-activation parity mode (ACE_MI_QUANT_ACT=q8) multiplies the block "
                           "weights themselves and cannot run an adapter");
-    const std::string lokr_file = lokr_weights_file(dir);
-    if (!lokr_file.empty()) return load_lokr(lokr_file, scale, max_layers, s);
-    auto ad = std::make_unique<LoraAdapter>(read_lora_adapter(dir, model_.cfg, max_layers));  // throws: state unchanged
+    auto next = std::make_unique<DitAdapter>(dir, model_.cfg, max_layers);  // throws: state unchanged
+    next->scale = scale;
     ACEMI_HIP(hipDeviceSynchronize());
-    free_lora();
-    // A and B of every module in one device buffer (256-byte aligned parts)
-    size_t total = 0;
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    for (const LoraModule& lm : ad->modules) total += al(lm.A.size() * 4) + al(lm.B.size() * 4);
-    std::vector<char> host(total);
-    lora_ab_.ensure(total);
-    size_t off = 0;
-    for (LoraModule& lm : ad->modules) {
-        std::memcpy(&host[off], lm.A.data(), lm.A.size() * 4);
-        lora_a_.push_back(reinterpret_cast<const float*>(lora_ab_.as<char>() + off));
-        off += al(lm.A.size() * 4);
-        std::memcpy(&host[off], lm.B.data(), lm.B.size() * 4);
-        lora_b_.push_back(reinterpret_cast<const float*>(lora_ab_.as<char>() + off));
-        off += al(lm.B.size() * 4);
-        lm.A = std::vector<float>();
-        lm.B = std::vector<float>();
-    }
-    ACEMI_HIP(hipMemcpy(lora_ab_.p, host.data(), total, hipMemcpyHostToDevice));
-    ACEMI_HIP(hipDeviceSynchronize());  // null-stream copy: done before any stream reads it
-    lora_ = std::move(ad);
-    lora_scale_ = scale;
+    images_.adapted.clear();
+    adapter_ = std::move(next);
     try {
         rebuild_lora_images(s);
     } catch (...) {
-        free_lora();
-        throw;
-    }
-}
-
-// A LyCORIS LoKr adapter (runtime/lokr.h): the stored factors in lora_ab_, the products' workspace in lokr_ws_.
-void DitEngine::load_lokr(const std::string& file, float scale, int max_layers, hipStream_t s) {
-    auto ad = std::make_unique<LokrAdapter>(read_lokr_adapter(file, model_.cfg, max_layers));  // throws: state unchanged
-    ACEMI_HIP(hipDeviceSynchronize());
-    free_lora();
-    size_t total = 0, ws = 0;
-    auto al = [](size_t b) { return (b + 255) & ~size_t(255); };
-    for (const LokrModule& km : ad->modules)
-        for (const auto& v : km.f) total += v.empty() ? 0 : al(v.size() * 4);
-    std::vector<char> host(total);
-    lora_ab_.ensure(total);
-    size_t off = 0;
-    for (LokrModule& km : ad->modules) {
-        for (auto& v : km.f) {
-            lokr_f_.push_back(v.empty() ? nullptr : reinterpret_cast<const float*>(lora_ab_.as<char>() + off));
-            if (v.empty()) continue;
-            std::memcpy(&host[off], v.data(), v.size() * 4);
-            off += al(v.size() * 4);
-            v = std::vector<float>();
-        }
-        LokrMergeJob shape;  // the workspace layout is the job's
-        shape.a = km.a, shape.b = km.b, shape.c = km.c, shape.d = km.d;
-        const float* const* f = &lokr_f_[lokr_f_.size() - 6];
-        shape.w1 = f[0], shape.w2 = f[3];
-        lokr_ws_off_.push_back(ws);
-        ws += (lokr_ws_floats(shape) + 63) & ~size_t(63);
-    }
-    lokr_ws_.ensure(ws * 4);
-    ACEMI_HIP(hipMemcpy(lora_ab_.p, host.data(), total, hipMemcpyHostToDevice));
-    ACEMI_HIP(hipDeviceSynchronize());  // null-stream copy: done before any stream reads it
-    lokr_ = std::move(ad);
-    lora_scale_ = scale;
-    try {
-        rebuild_lora_images(s);
-    } catch (...) {
-        free_lora();
+        adapter_.reset();
+        images_.adapted.clear();
+        images_.adapter_on = false;
         throw;
     }
 }
 
 void DitEngine::set_lora_scale(float scale, hipStream_t s) {
-    ACEMI_CHECK(lora_ != nullptr || lokr_ != nullptr, "lora not loaded");
-    lora_scale_ = scale;
+    ACEMI_CHECK(adapter_ != nullptr, "lora not loaded");
+    adapter_->scale = scale;
     rebuild_lora_images(s);
 }
 
 void DitEngine::unload_lora(hipStream_t s) {
     ACEMI_HIP(hipDeviceSynchronize());
-    free_lora();
+    adapter_.reset();
+    images_.adapted.clear();
     rebuild_lora_images(s);  // (nothing loaded: drops what was computed from the adapted views)
 }
-
-#ifndef __HIP__
-// Host build of the runtime (no device compiler: the CPU tests' library, whose other launch_* are host loops too):
-// launch_lora_merge as plain loops with the arithmetic of kernels.h, on "device" memory that is host memory.  The
-// translation unit is compiled without FMA contraction, so each multiply and add below rounds on its own.
-static float merge_widen(int fmt, uint16_t b) {
-    if (fmt == WF_F16) return half_to_f32(b);
-    const uint32_t u = (uint32_t)b << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-static uint16_t merge_narrow(int fmt, float f) {
-    if (fmt == WF_F16) {
-        const _Float16 h = (_Float16)f;
-        uint16_t u;
-        std::memcpy(&u, &h, 2);
-        return u;
-    }
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 64u);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-
-void launch_lora_merge(const LoraMergeJob* jobs, int n, hipStream_t) {
-    for (int ji = 0; ji < n; ++ji) {
-        const LoraMergeJob& j = jobs[ji];
-        ACEMI_CHECK((j.fmt == WF_BF16 || j.fmt == WF_F16) && j.base && j.out && j.rows > 0 && j.cols > 0 &&
-                        j.r >= 0 && j.r <= LORA_MAX_RANK && (j.r == 0 || (j.A && j.B)),
-                    "lora_merge: bad job");
-        for (int fr = j.row0; fr < j.row0 + j.rows; ++fr) {
-            const int o = lora_module_row(j.map, j.row_off, j.half, j.rows_mod, j.r, fr);
-            const uint16_t* src = j.base + (int64_t)fr * j.ld_base;
-            uint16_t* dst = j.out + (int64_t)fr * j.ld_out;
-            if (o < 0) {
-                if (j.copy_rest && src != dst) std::memmove(dst, src, (size_t)j.cols * 2);
-                continue;
-            }
-            for (int i = 0; i < j.cols; ++i) {
-                volatile float acc = 0.f;  // (volatile: one rounded f32 per step, whatever the optimiser prefers)
-                for (int k = 0; k < j.r; ++k) {
-                    const float p = j.B[(int64_t)o * j.r + k] * j.A[(int64_t)k * j.cols + i];
-                    acc = acc + p;
-                }
-                const float t = j.eff * acc;
-                dst[i] = merge_narrow(j.fmt, merge_widen(j.fmt, src[i]) + t);
-            }
-        }
-    }
-}
-
-// launch_lokr_merge the same way (kernels.h LokrMergeJob): the product factors as rank-ordered chains into the job's
-// workspace, then one rounded multiply w1 * W2, one by eff and one rounded add per weight.
-void launch_lokr_merge(const LokrMergeJob* jobs, int n, hipStream_t) {
-    auto product = [](const float* L, const float* R, float* out, int m, int nn, int r) {
-        for (int o = 0; o < m; ++o)
-            for (int i = 0; i < nn; ++i) {
-                volatile float acc = 0.f;
-                for (int k = 0; k < r; ++k) {
-                    const float p = L[(int64_t)o * r + k] * R[(int64_t)k * nn + i];
-                    acc = acc + p;
-                }
-                out[(int64_t)o * nn + i] = acc;
-            }
-    };
-    for (int ji = 0; ji < n; ++ji) {
-        const LokrMergeJob& j = jobs[ji];
-        ACEMI_CHECK((j.fmt == WF_BF16 || j.fmt == WF_F16) && j.base && j.out && j.rows > 0 && j.cols > 0 && j.a >= 0,
-                    "lokr_merge: bad job");
-        const float *w1 = j.w1, *W2 = j.w2;
-        if (j.a > 0) {
-            ACEMI_CHECK(j.b > 0 && j.c > 0 && j.d > 0 && (int64_t)j.b * j.d == j.cols && (j.w1 || (j.w1a && j.w1b && j.r1 > 0)) &&
-                            (j.w2 || (j.w2a && j.w2b && j.r2 > 0)) && (lokr_ws_floats(j) == 0 || j.ws),
-                        "lokr_merge: bad factors");
-            if (!W2) product(j.w2a, j.w2b, j.ws, j.c, j.d, j.r2), W2 = j.ws;
-            if (!w1) product(j.w1a, j.w1b, j.ws + lokr_ws_w1_offset(j), j.a, j.b, j.r1), w1 = j.ws + lokr_ws_w1_offset(j);
-        }
-        const int rows_mod = j.a * j.c;
-        for (int fr = j.row0; fr < j.row0 + j.rows; ++fr) {
-            const int o = lora_module_row(j.map, j.row_off, j.half, rows_mod, rows_mod, fr);
-            const uint16_t* src = j.base + (int64_t)fr * j.ld_base;
-            uint16_t* dst = j.out + (int64_t)fr * j.ld_out;
-            if (o < 0) {
-                if (j.copy_rest && src != dst) std::memmove(dst, src, (size_t)j.cols * 2);
-                continue;
-            }
-            for (int i = 0; i < j.cols; ++i) {
-                volatile float v = w1[(int64_t)(o / j.c) * j.b + i / j.d] * W2[(int64_t)(o % j.c) * j.d + i % j.d];
-                volatile float t = j.eff * v;
-                dst[i] = merge_narrow(j.fmt, merge_widen(j.fmt, src[i]) + t);
-            }
-        }
-    }
-}
-#endif
 
 }  // namespace acemi

@@ -19,8 +19,7 @@
 
 namespace acemi {
 
-struct LoraAdapter;  // runtime/lora.h
-struct LokrAdapter;  // runtime/lokr.h
+class DitAdapter;  // runtime/adapter.h
 
 struct ForwardIO {
     int B = 1, T = 0, L = 0;
@@ -113,10 +112,12 @@ class DitEngine {
     // launch only the MLP gate/up GEMM of layer 0 for a given M (bench / roofline probe)
     void probe_gemm(int which, int M, int iters, hipStream_t s);
     // PEFT LoRA adapter (runtime/lora.h reads it): every fused block matrix / the cross k|v
-    // matrix that holds a targeted module gets an adapted 16-bit image (launch_lora_merge; a quantized matrix is
-    // expanded to its bf16 image first and merged in place), which the GEMMs read from then on (weight_images.h): same
-    // kernels, same launches, nothing per step.  A scale change rebuilds from the base weights and unload is exact.
-    // All three block until the device is idle.  max_layers: ACE_GGML_DIT_MAX_LAYERS.
+    // matrix that holds a targeted module gets an adapted 16-bit image (the adapter's merge kernel; a quantized matrix
+    // is expanded to its bf16 image first and merged in place), which the GEMMs read from then on (weight_images.h):
+    // same kernels, same launches, nothing per step.  A scale change rebuilds from the base weights and unload is exact.
+    // All three block until the device is idle.  max_layers: ACE_GGML_DIT_MAX_LAYERS.  load_lora reads and uploads
+    // the new adapter before it releases a loaded one (a failed load leaves the state as it was), so for that moment
+    // both adapters' factor buffers are resident (tens of MB; the images are released before the new ones are built).
     // load_lora also takes a LyCORIS LoKr adapter (runtime/lokr.h: a directory with lokr_weights.safetensors and no
     // adapter_config.json, or that file): same images, built by launch_lokr_merge; it replaces a loaded LoRA adapter
     // and the other way round, so the two are never applied together.  For LoKr, LoraInfo's ranks are those of the
@@ -131,7 +132,7 @@ class DitEngine {
     void load_lora(const std::string& dir, float scale, int max_layers, hipStream_t s);
     void set_lora_scale(float scale, hipStream_t s);
     void unload_lora(hipStream_t s);
-    bool lora_loaded() const { return lora_ != nullptr || lokr_ != nullptr; }
+    bool lora_loaded() const { return adapter_ != nullptr; }
     LoraInfo lora_info() const;
 
    private:
@@ -191,22 +192,10 @@ class DitEngine {
                              hipStream_t s);
     // Which bytes a GEMM reads for a weight (resident, staged / kept bf16 image, adapted image): weight_images.h.
     WeightImages images_{model_};
-    // LoRA state: the adapter's A / B in one device buffer (lora_ab_); the adapted images are in
-    // images_, read while an adapter is loaded at a non-zero scale
-    std::unique_ptr<LoraAdapter> lora_;
-    std::vector<const float*> lora_a_, lora_b_;  // device A / B of lora_->modules[i]
-    DevBuf lora_ab_;
-    // LoKr state: the factors of lokr_->modules[i] at lokr_f_[6 * i + {w1, w1a, w1b, w2, w2a, w2b}] (null: not
-    // stored) inside lora_ab_, and the f32 workspace of the products (lokr_ws_, module i at lokr_ws_off_[i])
-    std::unique_ptr<LokrAdapter> lokr_;
-    std::vector<const float*> lokr_f_;
-    std::vector<size_t> lokr_ws_off_;
-    DevBuf lokr_ws_;
-    void load_lokr(const std::string& file, float scale, int max_layers, hipStream_t s);
-    float lora_scale_ = 0.f;
-    double lora_merge_ms_ = 0.0;
+    // The loaded adapter of either kind with its device factors, scale and merge time (runtime/adapter.h); the adapted
+    // images are in images_, read while an adapter is loaded at a non-zero scale
+    std::unique_ptr<DitAdapter> adapter_;
     void rebuild_lora_images(hipStream_t s);
-    void free_lora();
     struct Fault {  // ACE_MI_TEST_FAULT (test-only fault injection); layer -1 = off
         int layer = -1, row = 0, col = 0;
         float amp = 0.f;

@@ -20,13 +20,9 @@
 
 namespace acemi {
 
-struct LokrModule {
-    std::string name;  // lycoris_layers_{i}_{self_attn|cross_attn|mlp}_{x}_proj
-    int layer = 0, block = 0, proj = 0;
-    int in = 0, out = 0;
+struct LokrModule : AdapterModule {  // name: lycoris_layers_{i}_{self_attn|cross_attn|mlp}_{x}_proj
     int a = 0, b = 0, c = 0, d = 0, r1 = 0, r2 = 0;  // r1 / r2 = 0: w1 / W2 stored whole
-    float alpha = 0.f, scalar = 1.f;
-    float unit = 0.f;  // eff = scale * unit
+    float scalar = 1.f;
     std::vector<float> f[6];  // w1, w1_a, w1_b, w2, w2_a, w2_b (empty: not stored)
     bool has_alpha = false;
 };

@@ -26,12 +26,16 @@ struct InvalidArg : std::runtime_error {
 enum LoraBlock : int { LORA_SELF = 0, LORA_CROSS = 1, LORA_MLP = 2 };
 enum LoraProj : int { LORA_Q = 0, LORA_K = 1, LORA_V = 2, LORA_O = 3, LORA_GATE = 4, LORA_UP = 5, LORA_DOWN = 6 };
 
-struct LoraModule {
-    std::string name;  // layers.{i}.{self_attn|cross_attn|mlp}.{x}_proj
+struct AdapterModule {  // what the engine needs of a module of either adapter kind (runtime/adapter.h)
+    std::string name;
     int layer = 0, block = 0, proj = 0;
-    int r = 0, in = 0, out = 0;
+    int in = 0, out = 0;
     float alpha = 0.f;
-    float unit = 0.f;  // alpha / r or alpha / sqrt(r): eff = scale * unit
+    float unit = 0.f;  // eff = scale * unit
+};
+
+struct LoraModule : AdapterModule {  // name: layers.{i}.{self_attn|cross_attn|mlp}.{x}_proj
+    int r = 0;                       // unit = alpha / r or alpha / sqrt(r)
     std::vector<float> A, B;
     std::string a_key, b_key;
 };

@@ -543,136 +543,120 @@ ace_ggml_status ace_mi_bench_dequant_blocks(int32_t type, int32_t planes, int32_
     return ACE_GGML_OK;
 }
 
-// LoRA merge kernel: n_jobs jobs of one launch on one host matrix pair (include/acestep_mi355x_selftest.h).
-ace_ggml_status ace_mi_kernel_lora_merge(int32_t fmt, int32_t total_rows, int32_t cols, int32_t ld_base, int32_t ld_out,
-                                         const uint16_t* base, uint16_t* out, const ace_mi_lora_job* jobs,
-                                         int32_t n_jobs) {
+}  // extern "C"
+
+namespace {
+
+using MergeMem = std::vector<std::unique_ptr<DevMem>>;
+// n floats on the device, filled from h; h null: nothing (null) unless alloc, then n floats of workspace
+float* merge_floats(MergeMem& mem, const float* h, size_t n, bool alloc = false) {
+    if (!h && !alloc) return nullptr;
+    mem.emplace_back(new DevMem(h, n * 4));
+    return mem.back()->as<float>();
+}
+
+// What the two adapter merge entries share (include/acestep_mi355x_selftest.h): the checks on the host matrices and on
+// every job's row range, base / out on the device, each job's MergeTarget, one launch call, out back on the host.
+// valid(job) says whether the kind's operands are usable; fill(job, device job, mem) uploads them.
+template <typename HostJob, typename Job, typename Valid, typename Fill>
+ace_ggml_status merge_selftest(const char* who, int32_t fmt, int32_t total_rows, int32_t cols, int32_t ld_base,
+                               int32_t ld_out, const uint16_t* base, uint16_t* out, const HostJob* jobs, int32_t n_jobs,
+                               Valid valid, Fill fill, void (*launch)(const Job*, int, hipStream_t)) {
     using namespace acemi;
     if (!out || !jobs || n_jobs <= 0 || total_rows <= 0 || cols <= 0 || ld_out < cols || (base && ld_base < cols) ||
         (fmt != 0 && fmt != 1))
         return ACE_GGML_ERR_INVALID_ARG;
     for (int i = 0; i < n_jobs; ++i) {  // every row a job may touch lies inside the host matrices
-        const ace_mi_lora_job& j = jobs[i];
-        if (j.row0 < 0 || j.rows <= 0 || j.row0 + j.rows > total_rows || j.r < 0 || (j.r > 0 && (!j.A || !j.B || j.rows_mod <= 0)))
-            return ACE_GGML_ERR_INVALID_ARG;
+        const HostJob& j = jobs[i];
+        if (j.row0 < 0 || j.rows <= 0 || j.row0 + j.rows > total_rows || !valid(j)) return ACE_GGML_ERR_INVALID_ARG;
     }
     try {
         const size_t nb = (size_t)total_rows * (base ? ld_base : ld_out) * 2, no = (size_t)total_rows * ld_out * 2;
-        DevMem dbase(base ? nb : 16), dout(no);
-        if (base) ACEMI_HIP(hipMemcpy(dbase.p, base, nb, hipMemcpyHostToDevice));
-        ACEMI_HIP(hipMemcpy(dout.p, out, no, hipMemcpyHostToDevice));
-        std::vector<std::unique_ptr<DevMem>> ab;
-        std::vector<LoraMergeJob> lj(n_jobs);
+        DevMem dbase(base, base ? nb : 16), dout(out, no);
+        MergeMem mem;
+        std::vector<Job> dj(n_jobs);
         for (int i = 0; i < n_jobs; ++i) {
-            const ace_mi_lora_job& j = jobs[i];
-            LoraMergeJob& d = lj[i];
-            d.fmt = fmt == 1 ? WF_F16 : WF_BF16;
-            d.base = base ? dbase.as<uint16_t>() : dout.as<uint16_t>();
-            d.ld_base = base ? ld_base : ld_out;
-            d.out = dout.as<uint16_t>();
-            d.ld_out = ld_out;
-            d.row0 = j.row0;
-            d.rows = j.rows;
-            d.cols = cols;
-            d.r = j.r;
-            d.rows_mod = j.rows_mod;
-            d.eff = j.eff;
-            d.map = j.map;
-            d.row_off = j.row_off;
-            d.half = j.half;
-            d.copy_rest = j.copy_rest != 0;
-            if (j.r > 0) {
-                const size_t na = (size_t)j.r * cols * 4, nbb = (size_t)j.rows_mod * j.r * 4;
-                ab.emplace_back(new DevMem(na));
-                ACEMI_HIP(hipMemcpy(ab.back()->p, j.A, na, hipMemcpyHostToDevice));
-                d.A = ab.back()->as<float>();
-                ab.emplace_back(new DevMem(nbb));
-                ACEMI_HIP(hipMemcpy(ab.back()->p, j.B, nbb, hipMemcpyHostToDevice));
-                d.B = ab.back()->as<float>();
-            }
+            const HostJob& j = jobs[i];
+            MergeTarget& t = dj[i].t;
+            t.fmt = fmt == 1 ? WF_F16 : WF_BF16;
+            t.base = base ? dbase.as<uint16_t>() : dout.as<uint16_t>();
+            t.ld_base = base ? ld_base : ld_out;
+            t.out = dout.as<uint16_t>();
+            t.ld_out = ld_out;
+            t.row0 = j.row0;
+            t.rows = j.rows;
+            t.cols = cols;
+            t.map = j.map;
+            t.row_off = j.row_off;
+            t.half = j.half;
+            t.copy_rest = j.copy_rest != 0;
+            dj[i].eff = j.eff;
+            fill(j, dj[i], mem);
         }
         ACEMI_HIP(hipDeviceSynchronize());
-        launch_lora_merge(lj.data(), n_jobs, nullptr);
+        launch(dj.data(), n_jobs, nullptr);
         ACEMI_HIP(hipDeviceSynchronize());
-        ACEMI_HIP(hipMemcpy(out, dout.p, no, hipMemcpyDeviceToHost));
+        dout.to_host(out, no);
     } catch (const std::exception& ex) {
-        std::fprintf(stderr, "ace_mi_kernel_lora_merge: %s\n", ex.what());
+        std::fprintf(stderr, "%s: %s\n", who, ex.what());
         return ACE_GGML_ERR;
     }
     return ACE_GGML_OK;
 }
 
-// LoKr merge kernels: n_jobs jobs of one launch_lokr_merge call on one host matrix pair (include/acestep_mi355x_selftest.h).
+}  // namespace
+
+extern "C" {
+
+// LoRA merge kernel: n_jobs jobs of one launch on one host matrix pair.
+ace_ggml_status ace_mi_kernel_lora_merge(int32_t fmt, int32_t total_rows, int32_t cols, int32_t ld_base, int32_t ld_out,
+                                         const uint16_t* base, uint16_t* out, const ace_mi_lora_job* jobs,
+                                         int32_t n_jobs) {
+    using namespace acemi;
+    return merge_selftest(
+        "ace_mi_kernel_lora_merge", fmt, total_rows, cols, ld_base, ld_out, base, out, jobs, n_jobs,
+        [](const ace_mi_lora_job& j) { return j.r >= 0 && (j.r == 0 || (j.A && j.B && j.rows_mod > 0)); },
+        [&](const ace_mi_lora_job& j, LoraMergeJob& d, MergeMem& mem) {
+            d.r = j.r;
+            d.rows_mod = j.rows_mod;
+            if (j.r <= 0) return;
+            d.A = merge_floats(mem, j.A, (size_t)j.r * cols);
+            d.B = merge_floats(mem, j.B, (size_t)j.rows_mod * j.r);
+        },
+        launch_lora_merge);
+}
+
+// LoKr merge kernels: n_jobs jobs of one launch_lokr_merge call on one host matrix pair.
 ace_ggml_status ace_mi_kernel_lokr_merge(int32_t fmt, int32_t total_rows, int32_t cols, int32_t ld_base, int32_t ld_out,
                                          const uint16_t* base, uint16_t* out, const ace_mi_lokr_job* jobs,
                                          int32_t n_jobs) {
     using namespace acemi;
-    if (!out || !jobs || n_jobs <= 0 || total_rows <= 0 || cols <= 0 || ld_out < cols || (base && ld_base < cols) ||
-        (fmt != 0 && fmt != 1))
-        return ACE_GGML_ERR_INVALID_ARG;
-    for (int i = 0; i < n_jobs; ++i) {  // every row a job may touch lies inside the host matrices
-        const ace_mi_lokr_job& j = jobs[i];
-        if (j.row0 < 0 || j.rows <= 0 || j.row0 + j.rows > total_rows || j.a < 0) return ACE_GGML_ERR_INVALID_ARG;
-        if (j.a > 0 && (j.b <= 0 || j.c <= 0 || j.d <= 0 || (int64_t)j.b * j.d != cols ||
-                        !(j.w1 || (j.w1a && j.w1b && j.r1 > 0)) || !(j.w2 || (j.w2a && j.w2b && j.r2 > 0))))
-            return ACE_GGML_ERR_INVALID_ARG;
-    }
-    try {
-        const size_t nb = (size_t)total_rows * (base ? ld_base : ld_out) * 2, no = (size_t)total_rows * ld_out * 2;
-        DevMem dbase(base, base ? nb : 16), dout(out, no);
-        std::vector<std::unique_ptr<DevMem>> mem;
-        auto up = [&](const float* h, size_t n) -> const float* {
-            if (!h) return nullptr;
-            mem.emplace_back(new DevMem(h, n * 4));
-            return mem.back()->as<float>();
-        };
-        std::vector<LokrMergeJob> lj(n_jobs);
-        for (int i = 0; i < n_jobs; ++i) {
-            const ace_mi_lokr_job& j = jobs[i];
-            LokrMergeJob& d = lj[i];
-            d.fmt = fmt == 1 ? WF_F16 : WF_BF16;
-            d.base = base ? dbase.as<uint16_t>() : dout.as<uint16_t>();
-            d.ld_base = base ? ld_base : ld_out;
-            d.out = dout.as<uint16_t>();
-            d.ld_out = ld_out;
-            d.row0 = j.row0;
-            d.rows = j.rows;
-            d.cols = cols;
-            d.eff = j.eff;
-            d.map = j.map;
-            d.row_off = j.row_off;
-            d.half = j.half;
-            d.copy_rest = j.copy_rest != 0;
-            if (j.a <= 0) continue;
+    return merge_selftest(
+        "ace_mi_kernel_lokr_merge", fmt, total_rows, cols, ld_base, ld_out, base, out, jobs, n_jobs,
+        [&](const ace_mi_lokr_job& j) {
+            return j.a >= 0 && (j.a == 0 || (j.b > 0 && j.c > 0 && j.d > 0 && (int64_t)j.b * j.d == cols &&
+                                             (j.w1 || (j.w1a && j.w1b && j.r1 > 0)) && (j.w2 || (j.w2a && j.w2b && j.r2 > 0))));
+        },
+        [](const ace_mi_lokr_job& j, LokrMergeJob& d, MergeMem& mem) {
+            if (j.a <= 0) return;
             d.a = j.a, d.b = j.b, d.c = j.c, d.d = j.d;
             if (j.w1) {
-                d.w1 = up(j.w1, (size_t)j.a * j.b);
+                d.w1 = merge_floats(mem, j.w1, (size_t)j.a * j.b);
             } else {
                 d.r1 = j.r1;
-                d.w1a = up(j.w1a, (size_t)j.a * j.r1);
-                d.w1b = up(j.w1b, (size_t)j.r1 * j.b);
+                d.w1a = merge_floats(mem, j.w1a, (size_t)j.a * j.r1);
+                d.w1b = merge_floats(mem, j.w1b, (size_t)j.r1 * j.b);
             }
             if (j.w2) {
-                d.w2 = up(j.w2, (size_t)j.c * j.d);
+                d.w2 = merge_floats(mem, j.w2, (size_t)j.c * j.d);
             } else {
                 d.r2 = j.r2;
-                d.w2a = up(j.w2a, (size_t)j.c * j.r2);
-                d.w2b = up(j.w2b, (size_t)j.r2 * j.d);
+                d.w2a = merge_floats(mem, j.w2a, (size_t)j.c * j.r2);
+                d.w2b = merge_floats(mem, j.w2b, (size_t)j.r2 * j.d);
             }
-            if (lokr_ws_floats(d) > 0) {
-                mem.emplace_back(new DevMem(lokr_ws_floats(d) * 4));
-                d.ws = mem.back()->as<float>();
-            }
-        }
-        ACEMI_HIP(hipDeviceSynchronize());
-        launch_lokr_merge(lj.data(), n_jobs, nullptr);
-        ACEMI_HIP(hipDeviceSynchronize());
-        dout.to_host(out, no);
-    } catch (const std::exception& ex) {
-        std::fprintf(stderr, "ace_mi_kernel_lokr_merge: %s\n", ex.what());
-        return ACE_GGML_ERR;
-    }
-    return ACE_GGML_OK;
+            if (lokr_ws_floats(d) > 0) d.ws = merge_floats(mem, nullptr, lokr_ws_floats(d), true);
+        },
+        launch_lokr_merge);
 }
 
 // Dequant-fused GEMM on ggml block rows W [N][K]: out = A(bf16) . bf16(dequant(W))^T (+ bias).
