@@ -57,7 +57,8 @@ SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_ker
                     "ace_mi_kernel_lm_skinny", "ace_mi_kernel_lm_embed", "ace_mi_kernel_lm_qkv_post",
                     "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention", "ace_mi_kernel_lm_attention_shared",
                     "ace_mi_kernel_lm_skinny_q",
-                    "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_select", "ace_mi_kernel_lm_cache_fanout",
+                    "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_skinny_blocks", "ace_mi_kernel_lm_embed_blocks",
+                    "ace_mi_kernel_lm_select", "ace_mi_kernel_lm_cache_fanout",
                     "ace_mi_kernel_conv_gemm", "ace_mi_kernel_conv_out", "ace_mi_kernel_pack_f16",
                     "ace_mi_rope_table", "ace_mi_rope_table_steps")
 
@@ -1211,8 +1212,10 @@ def _bind_lm_kernels(lib):
     lib.ace_mi_kernel_lm_embed_q.argtypes = [i32] * 4 + [u8p, ip, fp]
     lib.ace_mi_kernel_lm_select.argtypes = [ctypes.POINTER(AceMiKernelLmSelectArgs)]
     lib.ace_mi_kernel_lm_cache_fanout.argtypes = [i32] * 7 + [u16p, u16p, ip, u16p, u16p, ip]
+    lib.ace_mi_kernel_lm_skinny_blocks.argtypes = [i32, ctypes.POINTER(AceMiBlockSeg)] + [i32] * 7 + [u16p, fp, u16p, ip]
+    lib.ace_mi_kernel_lm_embed_blocks.argtypes = [i32] * 4 + [u8p, ip, fp]
     for name in ("skinny", "embed", "qkv_post", "prefill_kv", "attention", "attention_shared", "skinny_q", "embed_q",
-                 "select", "cache_fanout"):
+                 "skinny_blocks", "embed_blocks", "select", "cache_fanout"):
         getattr(lib, "ace_mi_kernel_lm_" + name).restype = ctypes.c_int
     return lib
 
@@ -1296,6 +1299,47 @@ def kernel_lm_embed_q(blocks: np.ndarray, qtype: str, ids: np.ndarray, lib=None)
     _lm_status("embed_q", lib.ace_mi_kernel_lm_embed_q(QTYPES[qtype], i.shape[0], vocab, H,
                                                        b.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), _iptr(i),
                                                        _fptr(out)))
+    return out
+
+
+def kernel_lm_skinny_blocks(x_bits: np.ndarray, segs, y0: np.ndarray, epi: int = 0, n_rows=None, guard_rows: int = 0,
+                            lib=None, with_chain: bool = False):
+    """launch_lm_skinny_blocks on host arrays: x_bits [B][ldx] bf16 words; segs as kernel_dequant_segments takes them
+    (dicts qtype, blocks [guard_rows + rows + guard_rows][K / block][block bytes], row0, step, group), the guard rows
+    uploaded around each segment's own; n_rows (default: the rows the segments hold) is the N of the product.  y0 and
+    the result as kernel_lm_skinny_q."""
+    lib = _lm_lib(lib)
+    x = np.ascontiguousarray(x_bits, dtype=np.uint16)
+    keep = []
+    arr = (AceMiBlockSeg * len(segs))()
+    K, total = 0, 0
+    for i, g in enumerate(segs):
+        b, rows, K = _block_rows(g["blocks"], g["qtype"])
+        keep.append(b)
+        total += rows - 2 * guard_rows
+        arr[i] = AceMiBlockSeg(type=GGML_BLOCK_TYPES[g["qtype"]], rows=rows - 2 * guard_rows, row0=int(g.get("row0", 0)),
+                               step=int(g.get("step", 1)), group=int(g.get("group", 1)),
+                               blocks=b.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)))
+    N = total if n_rows is None else int(n_rows)
+    y = np.array(y0, dtype=np.uint16 if epi == LM_EPI_SWIGLU else np.float32, order="C", copy=True)
+    chain = ctypes.c_int32(0)
+    st = lib.ace_mi_kernel_lm_skinny_blocks(len(segs), arr, guard_rows, epi, x.shape[0], N, K, x.shape[1], y.shape[1],
+                                            _u16ptr(x), None if epi == LM_EPI_SWIGLU else _fptr(y),
+                                            _u16ptr(y) if epi == LM_EPI_SWIGLU else None, ctypes.byref(chain))
+    _lm_status("skinny_blocks", st)
+    return (y, int(chain.value)) if with_chain else y
+
+
+def kernel_lm_embed_blocks(blocks: np.ndarray, qtype: str, ids: np.ndarray, lib=None) -> np.ndarray:
+    """launch_lm_embed_blocks: raw blocks uint8 [vocab][H / block][block bytes] of any block type, ids [n] int32 -> f32
+    [n][H]."""
+    lib = _lm_lib(lib)
+    b, vocab, H = _block_rows(blocks, qtype)
+    i = np.ascontiguousarray(ids, dtype=np.int32)
+    out = np.full((i.shape[0], H), np.nan, dtype=np.float32)
+    _lm_status("embed_blocks", lib.ace_mi_kernel_lm_embed_blocks(GGML_BLOCK_TYPES[qtype], i.shape[0], vocab, H,
+                                                                 b.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                                                 _iptr(i), _fptr(out)))
     return out
 
 

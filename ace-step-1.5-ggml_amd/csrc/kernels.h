@@ -75,7 +75,8 @@ struct GemmEpilogue {
 // activation written as [hi | hi | lo] (Ah.Wh + Ah.Wl + Al.Wh) by the plain fp16 GEMM over 3K.
 // WF_GGML_RAW: raw ggml block rows exactly as the GGUF file holds them, as a list of row segments (BlockSeg below),
 // each with its own ggml type.  No GEMM reads this format: launch_dequant_blocks expands it to the dense bf16 image
-// first (the staged-dequant scopes of runtime/engine.h), and a bf16 activation multiplies that image.
+// first (the staged-dequant scopes of runtime/engine.h), and a bf16 activation multiplies that image.  The LM's decode
+// step alone multiplies the blocks themselves (launch_lm_skinny_blocks below).
 enum WeightFormat : int {
     WF_BF16 = 0, WF_F16 = 1, WF_Q8_0 = 2, WF_Q4_K = 3, WF_Q6_K = 4, WF_F32X3 = 5, WF_GGML_RAW = 6
 };
@@ -478,6 +479,19 @@ int lm_skinny_q_chain(int fmt, int K);
 constexpr int LM_EMBED_F32 = 100;
 void launch_lm_embed_q(int fmt, const void* q, const float* s, const int32_t* ids, int n, int vocab, int H, float* out,
                        hipStream_t stream);
+// The same two operations on a weight in raw ggml blocks (kernels/lm_decode_blocks.hip): W.fmt WF_GGML_RAW, its row
+// segments of any of launch_dequant_blocks' eleven types (src 16-byte aligned and readable up to the next 16-byte
+// boundary after its last block, as there), K a multiple of every segment's block.  The weight value multiplied is the
+// bf16 word launch_dequant_blocks writes for it; epilogues and fixed reduction order are launch_lm_skinny's, and on the
+// expanded image launch_lm_skinny returns the same bits.  LM_EPI_SWIGLU: two segments, the gate rows (row0 0) and the
+// up rows (row0 16) of the 16-row interleave (group 16, step 2, N / 2 rows each), which may differ in type.
+void launch_lm_skinny_blocks(const uint16_t* x, int ldx, int B, const WeightView& W, int N, int K, int epi, float* y_f32,
+                             uint16_t* y_act, int ldy, hipStream_t s);
+// longest f32 addition chain behind one output of launch_lm_skinny_blocks (its lane mapping: lm_decode_blocks.hip's header)
+int lm_skinny_blocks_chain(int type, int K);
+// rows of a raw-block table of one segment (rows = vocab, row0 0, step 1) as ggml's get_rows returns them: the f32
+// dequant (quant::dequantize_rows' arithmetic, not rounded to bf16), ids clamped into [0, vocab); out 16-byte aligned
+void launch_lm_embed_blocks(const WeightView& W, const int32_t* ids, int n, int vocab, int H, float* out, hipStream_t stream);
 // KV cache of one layer: k_cache / v_cache [B][hkv][capacity][128] fp16, key_mask [B][capacity] int32 (shared by the
 // layers).  qkv: the fused projection's f32 rows [.][ld] = [q heads | k heads | v heads]; rope_cos / rope_sin
 // [capacity][64].

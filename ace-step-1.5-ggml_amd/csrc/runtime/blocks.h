@@ -36,8 +36,13 @@ class BlockRunner {
     // qkv [B*n][ld] = [q | k | v] before the per-head norm and RoPE; what it enqueues on s runs before the
     // layer's attention prep (the causal LM's prefill fills its KV cache from here, runtime/lm.cpp)
     using AfterQkv = std::function<void(int li, float* qkv, int ld)>;
+    // operand (optional): called for every matrix immediately before its GEMM; the view it returns is the one the GEMM
+    // reads, and what it enqueues on s runs before that GEMM (the causal LM's raw-block mode expands a WF_GGML_RAW
+    // matrix into one reused bf16 scratch here: stream order keeps a GEMM ahead of the next expansion)
+    using Operand = std::function<WeightView(const DevWeight& w)>;
     void run(const BlockShape& sh, const std::vector<DevLayer>& layers, int n_layers, ActType act, int B, int n,
-             const int32_t* key_mask, bool causal, hipStream_t s, const AfterQkv* after_qkv = nullptr);
+             const int32_t* key_mask, bool causal, hipStream_t s, const AfterQkv* after_qkv = nullptr,
+             const Operand* operand = nullptr);
     // out = RMSNorm(x) * w (w null: a plain copy) for all B*n rows, or each item's token 0 when first_only
     void finish(const BlockShape& sh, const float* w, int B, int n, bool first_only, float* out, hipStream_t s);
 

@@ -122,6 +122,8 @@ class DevArena {
         items_.pop_back();
     }
     size_t bytes() const { return bytes_; }
+    // bytes() is a model's weight size: a loader takes the alignment padding of an upload off the count again
+    void uncount(size_t padding) { bytes_ -= padding; }
 
    private:
     struct Item {

@@ -8,6 +8,11 @@
 //                                 QKV post-processing, decode attention over the cache.  A matrix in ggml block planes
 //                                 (a GGUF checkpoint's Q8_0 / Q4_K / Q6_K tensors) goes through kernels/lm_decode_q.hip,
 //                                 which multiplies the bf16 values the prefill's quantized GEMM multiplies.
+//   ACE_MI_LM_RAW_BLOCKS=1        (read at ace_mi_load_lm, GGUF only) a matrix of any other block type, or a fused one
+//                                 of differing types, stays the file's raw blocks instead of a bf16 image: the step
+//                                 multiplies the blocks (kernels/lm_decode_blocks.hip), the prefill expands each such
+//                                 matrix into one reused bf16 scratch right before its GEMM -- the default mode's image,
+//                                 bit for bit, so the prefill's logits do not change.
 // Rounding points follow BlockRunner::run: the residual stream stays f32, the input of every linear is rounded to
 // the weights' 16-bit type, products accumulate in f32.  The one deviation: prefill attention reads Q, K, V as fp16
 // hi + lo pairs (~22 bits), the decode step keeps Q in f32 and reads K and V from the cache as single fp16 values.
@@ -19,6 +24,7 @@
 #include <vector>
 
 #include "../kernels/lm_attn_shared_host.h"  // empty under hipcc; the host build's launch_lm_attention_shared
+#include "../kernels/lm_decode_blocks_host.h"  // empty under hipcc; the host build's launch_lm_skinny_blocks / _embed_blocks
 #include "../kernels/lm_decode_q_host.h"  // empty under hipcc; the host build's launch_lm_skinny_q / launch_lm_embed_q
 #include "../kernels/lm_fanout_host.h"    // empty under hipcc; the host build's launch_lm_cache_fanout
 #include "../kernels/lm_sample_host.h"    // empty under hipcc; the host build's launch_lm_select
@@ -55,15 +61,25 @@ class LmEngine {
         return (size_t)c.layers * 2 * c.hkv * c.head_dim * 2;
     }
 
+    // ACE_MI_LM_RAW_BLOCKS=1, read once per load (before the loader runs)
+    bool read_raw_blocks_mode() {
+        const char* e = std::getenv("ACE_MI_LM_RAW_BLOCKS");
+        raw_blocks_ = e && std::atoi(e) != 0;
+        return raw_blocks_;
+    }
+
     void check_weights() const {
-        auto ok = [](const DevWeight& w) { return (w.fmt == WF_BF16 || w.fmt == WF_F16 || weight_planes(w.fmt)) && w.q; };
+        const bool raw_ok = raw_blocks_;
+        auto ok = [raw_ok](const DevWeight& w) {
+            return (w.fmt == WF_BF16 || w.fmt == WF_F16 || weight_planes(w.fmt) || (raw_ok && w.fmt == WF_GGML_RAW)) && w.q;
+        };
         for (const DevLayer& ly : model_.layers)
             for (const DevWeight* w : {&ly.w_qkv, &ly.w_o, &ly.w_gu, &ly.w_down})
                 if (!ok(*w)) throw Unsupported("LM weights must be dense BF16 / F16 or Q8_0 / Q4_K / Q6_K planes");
         if (!ok(model_.head)) throw Unsupported("LM head must be dense BF16 / F16 or Q8_0 / Q4_K / Q6_K planes");
         for (const DevLayer& ly : model_.layers)
             for (const DevWeight* w : {&ly.w_qkv, &ly.w_o, &ly.w_gu, &ly.w_down})
-                if (weight_planes(w->fmt) && model_.act != ActType::BF16)
+                if (weight_quantized(w->fmt) && model_.act != ActType::BF16)
                     throw Unsupported("mixed LM weight types: block planes take BF16 activations");
     }
 
@@ -85,6 +101,11 @@ class LmEngine {
         xn_.ensure((size_t)LM_MAX_BATCH * H * 4);
         xh_.ensure((size_t)LM_MAX_BATCH * H * 2);
         part_.ensure(lm_attn_part_floats(B, c.hq, cap) * 4);
+        size_t raw_image = 0;  // the prefill's expansion scratch: the largest raw-block layer matrix as bf16
+        for (const DevLayer& ly : model_.layers)
+            for (const DevWeight* w : {&ly.w_qkv, &ly.w_o, &ly.w_gu, &ly.w_down})
+                if (w->fmt == WF_GGML_RAW) raw_image = std::max(raw_image, (size_t)w->rows * w->cols * 2);
+        if (raw_image) raw_image_.ensure(raw_image);
         batch_ = B;
         capacity_ = cap;
         reset();
@@ -304,13 +325,17 @@ class LmEngine {
                 uint16_t* y_act, int ldy, hipStream_t s) {
         if (weight_planes(w.fmt))
             launch_lm_skinny_q(x, ldx, batch_, w.view(), N, K, epi, y_f32, y_act, ldy, s);
+        else if (w.fmt == WF_GGML_RAW)
+            launch_lm_skinny_blocks(x, ldx, batch_, w.view(), N, K, epi, y_f32, y_act, ldy, s);
         else
             launch_lm_skinny(t, x, ldx, batch_, static_cast<const uint16_t*>(w.q), N, K, epi, y_f32, y_act, ldy, s);
     }
 
     void embed(const int32_t* d_ids, int n, float* x, hipStream_t s) {
         const TextConfig& c = model_.cfg;
-        if (model_.embed_fmt == 3)
+        if (model_.embed_fmt == 4)
+            launch_lm_embed_blocks(model_.embed_q.view(), d_ids, n, c.vocab, c.hidden, x, s);
+        else if (model_.embed_fmt == 3)
             launch_lm_embed_q(model_.embed_q.fmt, model_.embed_q.q, model_.embed_q.s, d_ids, n, c.vocab, c.hidden, x, s);
         else if (model_.embed_fmt == 2)
             launch_lm_embed_q(LM_EMBED_F32, model_.embed, nullptr, d_ids, n, c.vocab, c.hidden, x, s);
@@ -350,7 +375,20 @@ class LmEngine {
         const BlockRunner::AfterQkv fill = [&](int li, float* qkv, int ld) {
             launch_lm_prefill_kv(post_args(li, qkv, ld), batch_, n, d_mask, s);
         };
-        blocks_.run(sh, model_.layers, c.layers, model_.act, batch_, n, d_mask, true, s, &fill);
+        // a raw-block matrix: its bf16 image (the default mode's resident one, bit for bit) into the scratch, on s
+        const BlockRunner::Operand expand = [&](const DevWeight& w) {
+            if (w.fmt != WF_GGML_RAW) return w.view();
+            uint16_t* img = raw_image_.as<uint16_t>();
+            std::vector<DequantBlocksJob> jobs;
+            for (const BlockSeg& g : w.segs) jobs.push_back(DequantBlocksJob{g, w.cols, w.cols, img});
+            launch_dequant_blocks(jobs.data(), (int)jobs.size(), s);
+            WeightView v;
+            v.fmt = WF_BF16;
+            v.q = img;
+            v.ld = w.cols;
+            return v;
+        };
+        blocks_.run(sh, model_.layers, c.layers, model_.act, batch_, n, d_mask, true, s, &fill, raw_blocks_ ? &expand : nullptr);
         head(x + (size_t)(n - 1) * sh.hidden, n, d_logits, s);
     }
 
@@ -404,6 +442,8 @@ class LmEngine {
     StopPoll poll_;  // declared before the buffers: the event and the pinned word go after the buffers are freed
     DevBuf kc_, vc_, kmask_, x_, act_, act2_, qkv_, q_, attn_, part_, xn_, xh_;
     DevBuf sel_work_, sel_next_, sel_done_, sel_uni_;  // selection scratch, the next step's ids, the stop words, uniforms
+    bool raw_blocks_ = false;  // ACE_MI_LM_RAW_BLOCKS at load: WF_GGML_RAW matrices are accepted and multiplied as blocks
+    DevBuf raw_image_;         // the prefill's bf16 image of one raw-block matrix at a time (workspace, not weights)
     RopeTable rope_;  // positions 0..capacity-1
     int batch_ = 0, capacity_ = 0, len_ = 0;
     // Set by fanout(copies > 1), cleared by begin, reset and prefill: sequences g * shared_group_ + s hold sequence
@@ -433,6 +473,7 @@ ace_ggml_status ace_mi_load_lm(ace_ggml_context* ctx, const char* model_dir) {
         opt.model_prefix = true;
         opt.lm_head = true;
         opt.lm_checkpoint = true;
+        opt.raw_blocks = eng->read_raw_blocks_mode();
         acemi::load_text_model(model_dir, eng->model(), opt);
         eng->check_weights();
         ctx->lm = std::move(eng);

@@ -78,6 +78,8 @@ struct Loader {
     // raw-block matrices (WF_GGML_RAW) are expanded to their bf16 image once, here, and only the image stays: the
     // condition / text encoders, whose block runner multiplies resident weights and has no staging scope
     bool raw_to_image = false;
+    // the LM's raw-block mode (ACE_MI_LM_RAW_BLOCKS): the blocks stay, and the arena counts their file bytes alone
+    bool count_file_bytes = false;
     std::string first_raw_name;  // first tensor kept as raw blocks, and its ggml type (the q8 mode's refusal)
     int first_raw_type = -1;
     explicit Loader(DevArena& a) : arena(a) {}
@@ -347,6 +349,11 @@ struct Loader {
             off += (p.bytes.size() + 15) & ~size_t(15);
         }
         uint8_t* base = arena.upload<uint8_t>(host.data(), host.size());
+        if (count_file_bytes) {
+            size_t file = 0;
+            for (const RawPart& p : a.parts) file += p.bytes.size();
+            arena.uncount(host.size() - file);
+        }
         for (size_t i = 0; i < a.parts.size(); ++i) {
             const RawPart& p = a.parts[i];
             BlockSeg g;

@@ -1,11 +1,12 @@
-// Kernel self-test entries of the LM decode kernels (kernels/lm_decode.hip, kernels/lm_decode_q.hip;
-// include/acestep_mi355x_selftest.h): one
+// Kernel self-test entries of the LM decode kernels (kernels/lm_decode.hip, kernels/lm_decode_q.hip,
+// kernels/lm_decode_blocks.hip; include/acestep_mi355x_selftest.h): one
 // launch_lm_* call on host buffers, blocking, so that tests/lm_kernel_cases.py can compare each kernel with a float64
 // reference of the same operation.  Built into libacestep_mi355x_selftest.so (Makefile target `selftest`) and, on top
 // of tests/host/lm_emul.cpp, into the LM host library (tests/lmhostlib.py); not part of runtime/selftest.cpp, which the
 // host library of tests/hostlib.py compiles without the LM kernels.
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "../../../include/acestep_mi355x_selftest.h"
@@ -100,6 +101,112 @@ ace_ggml_status ace_mi_kernel_lm_embed_q(int32_t qtype, int32_t n, int32_t vocab
         dout.to_host(out, no);
     } catch (const std::exception& ex) {
         std::fprintf(stderr, "ace_mi_kernel_lm_embed_q: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+namespace {
+
+// Row segments on the device as Loader::from_raw lays them out: one allocation, every segment 16-byte aligned and
+// padded to 16 bytes, 16 more at the end.  A segment's host blocks hold guard_rows + rows + guard_rows rows; the guard
+// rows' bytes lie directly before and after the segment's own (the front ones pushed up against its aligned start).
+struct DevSegs {
+    std::unique_ptr<DevMem> mem;
+    std::vector<acemi::BlockSeg> segs;
+    DevSegs(const ace_mi_block_seg* in, int n, int guard_rows, int K) {
+        std::vector<uint8_t> host;
+        std::vector<size_t> at;
+        for (int i = 0; i < n; ++i) {
+            const size_t rb = acemi::quant::row_bytes(acemi::quant::from_ggml(in[i].type), K);
+            const size_t front = (guard_rows * rb + 15) & ~size_t(15), all = (size_t)(in[i].rows + 2 * guard_rows) * rb;
+            const size_t start = host.size() + front - guard_rows * rb;
+            host.resize(((start + all + 15) & ~size_t(15)), 0);
+            std::memcpy(&host[start], in[i].blocks, all);
+            at.push_back(start + guard_rows * rb);
+        }
+        host.resize(host.size() + 16, 0);
+        mem.reset(new DevMem(host.data(), host.size()));
+        for (int i = 0; i < n; ++i) {
+            acemi::BlockSeg g;
+            g.type = in[i].type;
+            g.src = mem->as<uint8_t>() + at[(size_t)i];
+            g.rows = in[i].rows;
+            g.row0 = in[i].row0;
+            g.step = in[i].step;
+            g.group = in[i].group;
+            segs.push_back(g);
+        }
+    }
+    acemi::WeightView view() const {
+        acemi::WeightView v;
+        v.fmt = acemi::WF_GGML_RAW;
+        v.q = mem->p;
+        v.segs = segs.data();
+        v.n_segs = (int)segs.size();
+        return v;
+    }
+};
+
+bool block_segs_ok(const ace_mi_block_seg* segs, int n, int guard_rows, int K) {
+    if (!segs || n < 1 || guard_rows < 0) return false;
+    for (int i = 0; i < n; ++i) {
+        const auto q = acemi::quant::from_ggml(segs[i].type);
+        if (q == acemi::quant::QNONE || K < acemi::quant::block_values(q) || !acemi::quant::applies(q, K) || segs[i].rows < 1 ||
+            segs[i].row0 < 0 || segs[i].step < 1 || segs[i].group < 1 || !segs[i].blocks)
+            return false;
+    }
+    return true;
+}
+
+}  // namespace
+
+ace_ggml_status ace_mi_kernel_lm_skinny_blocks(int32_t n_segs, const ace_mi_block_seg* segs, int32_t guard_rows, int32_t epi,
+                                               int32_t B, int32_t N, int32_t K, int32_t ldx, int32_t ldy, const uint16_t* x,
+                                               float* y_f32, uint16_t* y_u16, int32_t* chain) {
+    using namespace acemi;
+    if (K < 32 || !block_segs_ok(segs, n_segs, guard_rows, K) || B < 1 || B > LM_MAX_BATCH || N < 1 || ldx % 8 != 0 || ldx < K ||
+        !x)
+        return ACE_GGML_ERR_INVALID_ARG;
+    const bool swiglu = epi == LM_EPI_SWIGLU;
+    if (swiglu ? (N % 32 != 0 || !y_u16) : ((epi != LM_EPI_STORE && epi != LM_EPI_RESID) || !y_f32))
+        return ACE_GGML_ERR_INVALID_ARG;
+    if (ldy < (swiglu ? N / 2 : N)) return ACE_GGML_ERR_INVALID_ARG;
+    for (int i = 0; i < n_segs; ++i) {
+        const BlockSeg g{segs[i].type, segs[i].blocks, segs[i].rows, segs[i].row0, segs[i].step, segs[i].group};
+        if (block_seg_row(g, g.rows - 1) >= N) return ACE_GGML_ERR_INVALID_ARG;
+    }
+    try {
+        const size_t ny = (size_t)B * ldy * (swiglu ? 2 : 4);
+        void* y = swiglu ? (void*)y_u16 : (void*)y_f32;
+        DevSegs dW(segs, n_segs, guard_rows, K);
+        DevMem dx(x, (size_t)B * ldx * 2), dy(y, ny);
+        launch_lm_skinny_blocks(dx.as<uint16_t>(), ldx, B, dW.view(), N, K, epi, swiglu ? nullptr : dy.as<float>(),
+                                swiglu ? dy.as<uint16_t>() : nullptr, ldy, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dy.to_host(y, ny);
+        if (chain) *chain = lm_skinny_blocks_chain(segs[0].type, K);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_skinny_blocks: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_kernel_lm_embed_blocks(int32_t type, int32_t n, int32_t vocab, int32_t H, const uint8_t* blocks,
+                                              const int32_t* ids, float* out) {
+    using namespace acemi;
+    const ace_mi_block_seg g{type, vocab, 0, 1, 1, blocks};
+    if (H < 32 || !block_segs_ok(&g, 1, 0, H) || n < 1 || !ids || !out) return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const size_t no = (size_t)n * H * 4;
+        DevSegs dW(&g, 1, 0, H);
+        DevMem di(ids, (size_t)n * 4), dout(out, no);
+        launch_lm_embed_blocks(dW.view(), di.as<int32_t>(), n, vocab, H, dout.as<float>(), nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dout.to_host(out, no);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_embed_blocks: %s\n", ex.what());
         return ACE_GGML_ERR;
     }
     return ACE_GGML_OK;

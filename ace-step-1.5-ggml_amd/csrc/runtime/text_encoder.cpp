@@ -87,7 +87,9 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
     // get_quant_type_from_env (qwen_model.cpp:38-44); the GGUF loaders keep the file's types
     L.qt = gguf_path.empty() ? quant::from_env("ACE_GGML_QWEN_WEIGHT_QTYPE") : quant::QNONE;
     m.qtype = L.qt;
-    L.raw_to_image = true;  // GGUF block types without a plane layout: expanded once to bf16 (loader.h)
+    const bool keep_raw = opt.raw_blocks && opt.lm_checkpoint && !gguf_path.empty();
+    L.raw_to_image = !keep_raw;  // GGUF block types without a plane layout: expanded once to bf16 (loader.h)
+    L.count_file_bytes = keep_raw;
     if (!gguf_path.empty()) {
         L.gguf = true;
         L.gg.open(gguf_path);
@@ -114,15 +116,19 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
         if (opt.lm_checkpoint && e.dtype == "Q") {  // the gather reads rows of the planes; a tied head shares them
             m.embed_q = L.from_blocks(e.qt, e.qblocks.data(), e.rows, e.cols);
             m.embed_fmt = 3;
+        } else if (keep_raw && e.dtype == "R") {  // the file's blocks: gathered from, and multiplied by a tied head
+            m.embed_q = L.finish(e);
+            m.embed_fmt = 4;
         } else if (e.dtype == "BF16" || e.dtype == "F16") {
             if (!quant::applies(L.qt, H)) {
                 m.embed_fmt = e.dtype == "BF16" ? 0 : 1;
                 m.embed = L.arena.upload<uint16_t>(e.u16.data(), e.u16.size() * 2);
             }
         }
-        if (!m.embed && m.embed_fmt != 3 && opt.lm_checkpoint && !L.gguf)
+        const bool in_blocks = m.embed_fmt == 3 || m.embed_fmt == 4;  // the table is embed_q
+        if (!m.embed && !in_blocks && opt.lm_checkpoint && !L.gguf)
             throw Unsupported("LM embed_tokens.weight has dtype " + e.dtype + " (16-bit BF16 / F16 only)");
-        if (!m.embed && m.embed_fmt != 3) {
+        if (!m.embed && !in_blocks) {
             std::vector<float> v = L.values(e);
             if (e.dtype != "Q" && quant::applies(L.qt, H)) {  // quantized at load, read back by get_rows
                 std::vector<uint8_t> blocks((size_t)c.vocab * quant::row_bytes(L.qt, H));
@@ -133,7 +139,7 @@ void load_text_model(const std::string& dir, TextModel& m, const TextLoadOptions
             m.embed = L.arena.upload<float>(v.data(), v.size() * 4);
         }
         if (opt.lm_head && !L.has("lm_head.weight") && c.tie_word_embeddings != 0) {  // the tied head: the table itself
-            if (m.embed_fmt == 3) {
+            if (m.embed_fmt == 3 || m.embed_fmt == 4) {
                 m.head = m.embed_q;
             } else if (m.embed_fmt != 2) {
                 m.head.fmt = m.embed_fmt == 1 ? WF_F16 : WF_BF16;

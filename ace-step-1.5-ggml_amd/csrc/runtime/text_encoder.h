@@ -22,8 +22,10 @@ struct TextConfig {
 struct TextModel {
     TextConfig cfg;
     void* embed = nullptr;  // [vocab][hidden]: bf16 / fp16 bits as stored, or f32 values (F32 or quantized)
-    int embed_fmt = 0;      // launch_embed_rows fmt: 0 bf16, 1 fp16, 2 f32; 3 (LM only): block planes in embed_q, embed null
-    DevWeight embed_q;      // embed_fmt 3: the table in Q8_0 / Q4_K / Q6_K planes (the gather reads rows of the planes)
+    int embed_fmt = 0;      // launch_embed_rows fmt: 0 bf16, 1 fp16, 2 f32; 3 / 4 (LM only): block planes / raw blocks in
+                            // embed_q, embed null
+    DevWeight embed_q;      // embed_fmt 3: the table in Q8_0 / Q4_K / Q6_K planes (the gather reads rows of the planes);
+                            // 4 (TextLoadOptions::raw_blocks): in raw blocks of any other block type
     float* norm = nullptr;  // [hidden]
     std::vector<DevLayer> layers;
     ActType act = ActType::BF16;
@@ -44,6 +46,10 @@ struct TextLoadOptions {
     // text encoder's keys are not consulted) and keeps its types; a safetensors checkpoint must be 16-bit (no
     // ACE_GGML_QWEN_WEIGHT_QTYPE, no F32 embed table: Unsupported); a plane-typed table stays in planes
     bool lm_checkpoint = false;
+    // ACE_MI_LM_RAW_BLOCKS=1 (ace_mi_load_lm with a GGUF only): a matrix, head or embed table that would become a bf16
+    // image (f32 table) out of block types -- a type without planes, a fused matrix of differing types -- stays
+    // WF_GGML_RAW, the file's bytes; the LM engine multiplies the blocks (kernels/lm_decode_blocks.hip)
+    bool raw_blocks = false;
 };
 
 // Throws std::runtime_error (the ABI reports ACE_GGML_ERR_IO like load_qwen_dir, acestep_ggml.cpp:238-244).

@@ -177,6 +177,19 @@ ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_skinny_q(int32_t qtype, int32_t ep
  * ids [n] clamped into the table. */
 ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_embed_q(int32_t qtype, int32_t n, int32_t vocab, int32_t H,
                                                       const uint8_t* blocks, const int32_t* ids, float* out);
+/* The same two on a weight in raw ggml blocks (csrc/kernels/lm_decode_blocks.hip): row segments as
+ * ace_mi_kernel_dequant_segments takes them (the ggml type ids listed there), laid out on the device as the loader
+ * does.  Each segment's blocks hold guard_rows + rows + guard_rows block rows: the guard rows are uploaded directly
+ * before and after the segment's own and must not reach the result.  epi 2: two segments, gate (row0 0) and up (row0
+ * 16), group 16, step 2.  *chain as above. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_skinny_blocks(int32_t n_segs, const ace_mi_block_seg* segs,
+                                                            int32_t guard_rows, int32_t epi, int32_t B, int32_t N,
+                                                            int32_t K, int32_t ldx, int32_t ldy, const uint16_t* x,
+                                                            float* y_f32, uint16_t* y_u16, int32_t* chain);
+/* Embedding rows from raw blocks of ggml type `type`: out [n][H] f32 = the f32 dequant (ggml get_rows) of blocks
+ * [vocab][row bytes] at ids [n] clamped into the table. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_embed_blocks(int32_t type, int32_t n, int32_t vocab, int32_t H,
+                                                           const uint8_t* blocks, const int32_t* ids, float* out);
 /* Decode step's q/k norm + RoPE + cache append at slot pos: qkv [B][ld] f32, q_norm / k_norm [128], rope_cos / rope_sin
  * [capacity][64], mask_new [B] or NULL; q_out [B][hq][128] f32; k_cache / v_cache [B][hkv][capacity][128] fp16 and
  * key_mask [B][capacity] (one layer) are in-out. */
