@@ -44,6 +44,7 @@ EXPORTED_SYMBOLS = (
     "ace_ggml_generate_audio_style_lyric_timbre_simple", "ace_mi_reference_noise",
     "ace_mi_load_lm", "ace_mi_lm_get_info", "ace_mi_lm_begin", "ace_mi_lm_forward", "ace_mi_lm_reset",
     "ace_mi_lm_select", "ace_mi_lm_generate", "ace_mi_lm_fanout", "ace_mi_lm_uniforms",
+    "ace_mi_lm_score",
 )
 
 # Every symbol declared in include/acestep_mi355x_selftest.h: the TEST library (libacestep_mi355x_selftest.so = the
@@ -58,7 +59,7 @@ SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_ker
                     "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention", "ace_mi_kernel_lm_attention_shared",
                     "ace_mi_kernel_lm_skinny_q",
                     "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_skinny_blocks", "ace_mi_kernel_lm_embed_blocks",
-                    "ace_mi_kernel_lm_select", "ace_mi_kernel_lm_cache_fanout",
+                    "ace_mi_kernel_lm_select", "ace_mi_kernel_lm_cache_fanout", "ace_mi_kernel_lm_score",
                     "ace_mi_kernel_conv_gemm", "ace_mi_kernel_conv_out", "ace_mi_kernel_pack_f16",
                     "ace_mi_rope_table", "ace_mi_rope_table_steps")
 
@@ -294,6 +295,8 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.ace_mi_lm_fanout.restype = ctypes.c_int
         lib.ace_mi_lm_uniforms.argtypes = [ctypes.c_uint64, i64, fp]
         lib.ace_mi_lm_uniforms.restype = ctypes.c_int
+        lib.ace_mi_lm_score.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+        lib.ace_mi_lm_score.restype = ctypes.c_int
     if path is None:
         _LIB = lib
     return lib
@@ -577,6 +580,32 @@ class GGMLCAPIBridge:
             self.lm_forward_device(ids.data_ptr(), am.data_ptr() if am is not None else 0, ids.shape[1],
                                    out.data_ptr(), stream)
         return out
+
+    def lm_score(self, input_ids, attention_mask=None, score_from: int = 1):
+        """Teacher-forced scoring (ace_mi_lm_score): prefill input_ids [B, n] on the empty cache and return
+        (logprob f32 [B, n - score_from], rank int32 [B, n - score_from]) on the ids' device: the log-probability of
+        token p given the tokens before it, and the number of ids the model ranks above it, for p = score_from .. n-1.
+        The cache then holds the n positions; tensors and stream rules as in lm_forward."""
+        import torch
+        from .hook import _OrderedCall
+        ids = input_ids.detach().to(torch.int32).contiguous()
+        if ids.dim() != 2:
+            raise ValueError("lm_score: input_ids must be [B, n]")
+        dev = ids.device
+        am = None
+        if attention_mask is not None:
+            am = (attention_mask.detach().to(dev) != 0).to(torch.int32).contiguous()
+            if am.shape != ids.shape:
+                raise ValueError("lm_score: attention_mask must cover exactly the columns of input_ids")
+        B, n = ids.shape
+        T = max(n - int(score_from), 0)
+        logprob = torch.empty((B, T), dtype=torch.float32, device=dev)
+        rank = torch.empty((B, T), dtype=torch.int32, device=dev)
+        with _OrderedCall(self, dev) as stream:
+            st = self.lib.ace_mi_lm_score(self.ctx, ids.data_ptr(), am.data_ptr() if am is not None else None, n,
+                                          int(score_from), logprob.data_ptr(), rank.data_ptr(), None, stream or None)
+            self._ensure_ok(st, "ace_mi_lm_score")
+        return logprob, rank
 
     def _lm_sample_params(self, dev, allowed_ids=None, stop_id=-1, min_tokens=0, cfg_scale=1.0, pre_temperature=0.0,
                           temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0):
@@ -1214,8 +1243,9 @@ def _bind_lm_kernels(lib):
     lib.ace_mi_kernel_lm_cache_fanout.argtypes = [i32] * 7 + [u16p, u16p, ip, u16p, u16p, ip]
     lib.ace_mi_kernel_lm_skinny_blocks.argtypes = [i32, ctypes.POINTER(AceMiBlockSeg)] + [i32] * 7 + [u16p, fp, u16p, ip]
     lib.ace_mi_kernel_lm_embed_blocks.argtypes = [i32] * 4 + [u8p, ip, fp]
+    lib.ace_mi_kernel_lm_score.argtypes = [i32] * 5 + [u16p, u16p, ip, fp, ip, ip, i32, fp]
     for name in ("skinny", "embed", "qkv_post", "prefill_kv", "attention", "attention_shared", "skinny_q", "embed_q",
-                 "skinny_blocks", "embed_blocks", "select", "cache_fanout"):
+                 "skinny_blocks", "embed_blocks", "select", "cache_fanout", "score"):
         getattr(lib, "ace_mi_kernel_lm_" + name).restype = ctypes.c_int
     return lib
 
@@ -1341,6 +1371,27 @@ def kernel_lm_embed_blocks(blocks: np.ndarray, qtype: str, ids: np.ndarray, lib=
                                                                  b.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                                                                  _iptr(i), _fptr(out)))
     return out
+
+
+def kernel_lm_score(x_bits: np.ndarray, w_bits: np.ndarray, target: np.ndarray, splits: int = 0, act_type: int = 0,
+                    reps: int = 0, lib=None):
+    """launch_lm_score on host arrays: x_bits [M][H] and w_bits [V][H] 16-bit words of act_type (0 bf16, 1 fp16),
+    target [M] int32, splits vocabulary runs per row block (0 = automatic).  Returns (logprob f32 [M], rank int32 [M],
+    chain) with chain the longest f32 addition chain behind one logit; with reps > 0 a fourth value, the mean
+    milliseconds of `reps` further launches."""
+    lib = _lm_lib(lib)
+    x = np.ascontiguousarray(x_bits, dtype=np.uint16)
+    w = np.ascontiguousarray(w_bits, dtype=np.uint16)
+    t = np.ascontiguousarray(target, dtype=np.int32)
+    if x.ndim != 2 or w.ndim != 2 or x.shape[1] != w.shape[1] or t.shape != (x.shape[0],):
+        raise ValueError("kernel_lm_score: inconsistent shapes")
+    logprob, rank = np.zeros(x.shape[0], np.float32), np.zeros(x.shape[0], np.int32)
+    chain, ms = ctypes.c_int32(0), ctypes.c_float(0.0)
+    st = lib.ace_mi_kernel_lm_score(act_type, x.shape[0], w.shape[0], x.shape[1], int(splits), _u16ptr(x), _u16ptr(w),
+                                    _iptr(t), _fptr(logprob), _iptr(rank), ctypes.byref(chain), int(reps),
+                                    ctypes.byref(ms))
+    _lm_status("score", st)
+    return (logprob, rank, chain.value) + ((ms.value,) if reps > 0 else ())
 
 
 def kernel_lm_cache_fanout(k_src: np.ndarray, v_src: np.ndarray, mask_src: np.ndarray, k_dst: np.ndarray,

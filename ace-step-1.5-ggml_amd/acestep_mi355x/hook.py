@@ -454,6 +454,21 @@ class EngineCausalLM:
 
     forward = __call__
 
+    def score(self, input_ids, attention_mask=None, score_from: int = 1):
+        """Teacher-forced scoring of input_ids [B, n] in one new prefill (bridge.lm_score): (logprob, rank) of the
+        tokens at score_from .. n-1, each [B, n - score_from].  The cache of that prefill becomes the live one (exactly
+        n positions are reserved), as after __call__ without past_key_values; no logits are kept."""
+        if input_ids is None or input_ids.dim() != 2:
+            raise ValueError("input_ids must be a [B, n] tensor")
+        B, n = int(input_ids.shape[0]), int(input_ids.shape[1])
+        self.bridge.lm_begin(B, n)
+        self._serial += 1
+        self._live = _LmCacheHandle(self._serial)
+        self._last_logits = None
+        out = self.bridge.lm_score(input_ids, attention_mask, score_from)
+        self._live.length += n
+        return out
+
     def generate_codes(self, n_codes: int, allowed_ids, eos_id: int, cfg_scale: float = 1.0, codes_temperature=None,
                        temperature: float = 1.0, top_k=None, top_p=None, repetition_penalty: float = 1.0,
                        prompt_ids=None, seed: int = 0, uniforms=None):
@@ -700,8 +715,47 @@ def _run_pt_fanout(handler, prompts, temperature, cfg_scale, negative_prompt, to
     return texts
 
 
+def _engine_target_scores(llm_handler, formatted_prompt: str, target_text: str):
+    """(logprob, rank) of the target's tokens given the prompt, 1-D CPU tensors, or None for an empty target: the
+    tokenisation of the reference's _get_logits_and_target_for_scoring (acestep/test_time_scaling.py:141-155: the prompt
+    alone for its length, then prompt + target in one piece), scored by EngineCausalLM.score instead of a forward that
+    returns every position's logits."""
+    import torch
+    tok = llm_handler.llm_tokenizer
+    prompt_len = int(tok(formatted_prompt, return_tensors="pt", add_special_tokens=True)["input_ids"].shape[1])
+    full = tok(formatted_prompt + target_text, return_tensors="pt", padding=False, truncation=True, add_special_tokens=True)
+    ids = full["input_ids"]
+    if ids.shape[1] <= prompt_len or prompt_len < 1:
+        return None
+    model = llm_handler.llm
+    dev = getattr(llm_handler, "device", None)   # the reference puts the ids on the handler's device
+    if dev is None or str(dev) == "auto":
+        dev = model.device
+    with torch.no_grad():
+        logprob, rank = model.score(ids.to(dev), full["attention_mask"].to(dev), prompt_len)
+    return logprob[0].cpu(), rank[0].cpu()
+
+
+def _install_scoring(scoring_module) -> None:
+    def log_prob_mi355x(llm_handler, formatted_prompt, target_text, temperature=1.0):
+        got = _engine_target_scores(llm_handler, formatted_prompt, target_text)
+        return float("-inf") if got is None else got[0].mean().item()
+
+    def topk_recall_mi355x(llm_handler, formatted_prompt, target_text, topk=10):
+        got = _engine_target_scores(llm_handler, formatted_prompt, target_text)
+        if got is None:
+            return 0.0, {}
+        rank = got[1].tolist()
+        recall_per_k = {k: sum(r < k for r in rank) / len(rank) for k in range(1, topk + 1)}
+        weights = [1.0 - r / topk if r < topk else 0.0 for r in rank]
+        return sum(weights) / len(weights), recall_per_k
+
+    scoring_module._calculate_log_prob = log_prob_mi355x
+    scoring_module._calculate_topk_recall = topk_recall_mi355x
+
+
 def install_lm_backend(llm_handler: Any, bridge, max_new_tokens: int = 4096, device_codes: bool = False,
-                       batch_codes: bool = False) -> None:
+                       batch_codes: bool = False, scoring_module=None) -> None:
     """Point the reference LLM handler's `pt` backend at the engine: `llm_handler.llm` becomes an EngineCausalLM over
     the LM that `bridge.load_lm` loaded (needs no `transformers`).
 
@@ -719,9 +773,18 @@ def install_lm_backend(llm_handler: Any, bridge, max_new_tokens: int = 4096, dev
     CODES_GENERATION with target_codes, eos_token_id and a mask right after its set-up (so no token is sampled before the
     code phase), runs in groups of 4 items under CFG (cfg_scale > 1), otherwise 8: one prefill, one cache fan-out and one
     generate_codes call per group (_run_pt_fanout), each item with the engine stream the sequential path would give
-    it, so the returned texts are the sequential path's.  Anything else runs the handler's own sequential `_run_pt`."""
+    it, so the returned texts are the sequential path's.  Anything else runs the handler's own sequential `_run_pt`.
+
+    scoring_module: the reference's scoring module object (acestep.test_time_scaling), or None.  Its forward over
+    prompt + target reads every position's logits, which the engine never returns (EngineCausalLM gives the last
+    position's), so with the engine installed its scores are empty.  When the module is given, its `_calculate_log_prob`
+    and `_calculate_topk_recall` (same signatures and return values, so `calculate_pmi_score_per_condition` runs as it
+    is) are replaced by functions that score the target with EngineCausalLM.score: one prefill, one fused head /
+    log-softmax / rank kernel, no [n, vocab] logits."""
     if batch_codes and not device_codes:
         raise ValueError("install_lm_backend: batch_codes=True needs device_codes=True")
+    if scoring_module is not None:
+        _install_scoring(scoring_module)
     device = getattr(llm_handler, "device", None)
     if device is None or str(device) in ("auto", "cpu"):
         device = "cuda"

@@ -2,6 +2,7 @@
 // allocation, no synchronisation: safe to capture into a hipGraph).
 #pragma once
 
+#include <algorithm>
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
@@ -625,6 +626,52 @@ void launch_lm_select(const LmSelectArgs& a, hipStream_t s);
 // longest f32 addition chains of launch_lm_select over n_cand candidates, three ints: [0] behind a top-p mass (and
 // behind the top-p total), [1] behind the draw's total, [2] behind a cumulative value of the draw
 void lm_select_chains(int n_cand, int* chains);
+
+// ------------------------------------------------------------ LM teacher-forced scoring (kernels/lm_score.hip)
+// Head product with a vocabulary reduction for an epilogue: with l_j = sum_k X[m][k] W[j][k] (f32 on the MFMA) and
+// t = clamp(target[m], 0, V - 1),
+//   logprob[m] = l_t - logsumexp_j l_j          rank[m] = #{ j != t : l_j > l_t or (l_j == l_t and j < t) }
+// The [M][V] logits exist only as accumulator tiles.  The vocabulary is cut into `splits` contiguous runs of 128-column
+// tiles, one workgroup per (64-row block, run); every wave leaves a (max, sum of exp, count) triple per row and a
+// second kernel merges the triples in a fixed order (no atomics: bit-identical between runs).  l_t comes from a first
+// pass of the same tile loop over the gathered rows W[t], so it has the bits the sweep computes for column t.
+struct LmScoreArgs {
+    const uint16_t* x = nullptr;  // [M][ldx] 16-bit activations of type `act`
+    int64_t ldx = 0;
+    const uint16_t* w = nullptr;  // [V][ldw] dense 16-bit head of the same type
+    int64_t ldw = 0;
+    int M = 0, V = 0, H = 0;      // H % 32 == 0
+    // target of row m: target[(m / t_group) * t_stride + m % t_group] (device values, clamped into [0, V))
+    const int32_t* target = nullptr;
+    int t_group = 1 << 30;
+    int64_t t_stride = 0;
+    int splits = 0;               // vocabulary runs per row block; 0 = lm_score_splits' choice
+    float* work = nullptr;        // lm_score_work_floats() floats of scratch
+    float* logprob = nullptr;     // [M]
+    int32_t* rank = nullptr;      // [M]
+};
+constexpr int LM_SCORE_BM = 64, LM_SCORE_BN = 128, LM_SCORE_MAX_SPLITS = 1024;
+// the split count of a launch: the caller's, else enough runs to give every CU two workgroups (256 CUs); never more
+// than LM_SCORE_MAX_SPLITS.  A run past the last tile is legal and leaves empty triples.
+inline int lm_score_splits(int M, int V, int splits) {
+    const int mblocks = (M + LM_SCORE_BM - 1) / LM_SCORE_BM, tiles = (V + LM_SCORE_BN - 1) / LM_SCORE_BN;
+    if (splits <= 0) splits = std::min(tiles, (512 + mblocks - 1) / mblocks);
+    return std::max(1, std::min(splits, LM_SCORE_MAX_SPLITS));
+}
+// scratch: l_t per row, then (max, sum, count) per row and partial; two partials (column halves of a tile) per split
+inline size_t lm_score_work_floats(int M, int V, int splits) {
+    return (size_t)M * (1 + 3 * 2 * (size_t)lm_score_splits(M, V, splits));
+}
+inline void lm_score_check(const LmScoreArgs& a) {
+    ACEMI_CHECK(a.x && a.w && a.target && a.work && a.logprob && a.rank, "lm_score: null buffer");
+    ACEMI_CHECK(a.M >= 1 && a.V >= 1 && a.H >= 32 && a.H % 32 == 0, "lm_score: bad shape (H must be a multiple of 32)");
+    ACEMI_CHECK(a.ldx >= a.H && a.ldw >= a.H && a.ldx % 8 == 0 && a.ldw % 8 == 0, "lm_score: bad leading dimension");
+    ACEMI_CHECK(a.t_group >= 1 && a.splits >= 0 && (int64_t)((a.M + LM_SCORE_BM - 1) / LM_SCORE_BM) * LM_SCORE_MAX_SPLITS < (1 << 30),
+                "lm_score: bad target grouping or split count");
+}
+void launch_lm_score(ActType act, const LmScoreArgs& a, hipStream_t s);
+// longest f32 addition chain behind one logit of launch_lm_score (MFMA: 32 values per instruction, then H / 32 adds)
+int lm_score_chain(int H);
 
 // ------------------------------------------------------------ VAE decoder (kernels/vae.hip)
 // Implicit-GEMM conv on fp16 time-major activations.  A row (m, tap) = S[m + tap*dil - pad]

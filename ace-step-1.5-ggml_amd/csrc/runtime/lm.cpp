@@ -20,6 +20,7 @@
 // This file holds both the engine and its C entries, so no other translation unit refers to the launch_lm_* kernels.
 #include <cmath>
 #include <cstdlib>
+#include <memory>
 #include <random>
 #include <vector>
 
@@ -28,6 +29,7 @@
 #include "../kernels/lm_decode_q_host.h"  // empty under hipcc; the host build's launch_lm_skinny_q / launch_lm_embed_q
 #include "../kernels/lm_fanout_host.h"    // empty under hipcc; the host build's launch_lm_cache_fanout
 #include "../kernels/lm_sample_host.h"    // empty under hipcc; the host build's launch_lm_select
+#include "../kernels/lm_score_host.h"     // empty under hipcc; the host build's launch_lm_score
 #include "context.h"
 #include "safetensors.h"
 
@@ -168,6 +170,16 @@ class LmEngine {
             prefill(d_ids, d_mask, n, d_logits, s);
         else
             step(d_ids, d_mask, d_logits, s);
+        len_ += n;
+    }
+
+    // Teacher-forced scoring (ace_mi_lm_score): the prefill of n positions, then rows score_from-1 .. n-2 of every
+    // sequence's final hidden state against the ids at score_from .. n-1 (kernels/lm_score.hip).  The caller has
+    // checked the arguments and the prefill rule; d_logits may be null.
+    void score(const int32_t* d_ids, const int32_t* d_mask, int n, int score_from, float* d_logprob, int32_t* d_rank,
+               float* d_logits, hipStream_t s) {
+        const ScoreOut out{score_from, d_logprob, d_rank};
+        prefill(d_ids, d_mask, n, d_logits, s, &out);
         len_ += n;
     }
 
@@ -364,7 +376,65 @@ class LmEngine {
         return sh;
     }
 
-    void prefill(const int32_t* d_ids, const int32_t* d_mask, int n, float* d_logits, hipStream_t s) {
+    struct ScoreOut {
+        int from;
+        float* logprob;
+        int32_t* rank;
+    };
+
+    // The head as a dense 16-bit image for launch_lm_score: a dense head in place; block planes and raw blocks
+    // expanded to the bf16 image the default mode keeps resident, into `scratch` (the caller frees it after the
+    // stream has finished).
+    const uint16_t* head_image(std::unique_ptr<DevMem>& scratch, hipStream_t s) {
+        const DevWeight& hw = model_.head;
+        if (hw.fmt == WF_BF16 || hw.fmt == WF_F16) return static_cast<const uint16_t*>(hw.q);
+        const TextConfig& c = model_.cfg;
+        scratch.reset(new DevMem((size_t)c.vocab * c.hidden * 2));
+        uint16_t* img = scratch->as<uint16_t>();
+        if (hw.fmt == WF_GGML_RAW) {
+            std::vector<DequantBlocksJob> jobs;
+            for (const BlockSeg& g : hw.segs) jobs.push_back(DequantBlocksJob{g, c.hidden, c.hidden, img});
+            launch_dequant_blocks(jobs.data(), (int)jobs.size(), s);
+        } else {
+            launch_dequant_bf16(hw.view(), c.vocab, c.hidden, img, s);
+        }
+        return img;
+    }
+
+    // rows [from - 1, n - 1) of every sequence of x [batch_][n][H]: head()'s final norm and rounding, then the scoring
+    // kernel against ids [from, n)
+    void score_rows(const float* x, const int32_t* d_ids, int n, const ScoreOut& o, hipStream_t s) {
+        const TextConfig& c = model_.cfg;
+        const ActType ht = model_.head.act();
+        const int T = n - o.from, M = batch_ * T, H = c.hidden;
+        sc_xn_.ensure((size_t)M * H * 4);
+        sc_xh_.ensure((size_t)M * H * 2);
+        sc_work_.ensure(lm_score_work_floats(M, c.vocab, 0) * 4);
+        for (int b = 0; b < batch_; ++b)
+            launch_rmsnorm_f32(x + ((size_t)b * n + o.from - 1) * H, T, 1, H, model_.norm, c.eps,
+                               sc_xn_.as<float>() + (size_t)b * T * H, s);
+        launch_to_act(ht, sc_xn_.as<float>(), (int64_t)M * H, false, sc_xh_.as<uint16_t>(), s);
+        std::unique_ptr<DevMem> scratch;
+        LmScoreArgs a;
+        a.x = sc_xh_.as<uint16_t>();
+        a.ldx = H;
+        a.w = head_image(scratch, s);
+        a.ldw = H;
+        a.M = M;
+        a.V = c.vocab;
+        a.H = H;
+        a.target = d_ids + o.from;
+        a.t_group = T;
+        a.t_stride = n;
+        a.work = sc_work_.as<float>();
+        a.logprob = o.logprob;
+        a.rank = o.rank;
+        launch_lm_score(ht, a, s);
+        if (scratch) ACEMI_HIP(hipStreamSynchronize(s));  // the sweep has read the image: it may go
+    }
+
+    void prefill(const int32_t* d_ids, const int32_t* d_mask, int n, float* d_logits, hipStream_t s,
+                 const ScoreOut* score = nullptr) {
         const TextConfig& c = model_.cfg;
         const BlockShape sh = shape();
         const int M = batch_ * n;
@@ -389,7 +459,8 @@ class LmEngine {
             return v;
         };
         blocks_.run(sh, model_.layers, c.layers, model_.act, batch_, n, d_mask, true, s, &fill, raw_blocks_ ? &expand : nullptr);
-        head(x + (size_t)(n - 1) * sh.hidden, n, d_logits, s);
+        if (d_logits) head(x + (size_t)(n - 1) * sh.hidden, n, d_logits, s);
+        if (score) score_rows(x, d_ids, n, *score, s);
     }
 
     void step(const int32_t* d_ids, const int32_t* d_mask, float* d_logits, hipStream_t s) {
@@ -444,6 +515,7 @@ class LmEngine {
     DevBuf sel_work_, sel_next_, sel_done_, sel_uni_;  // selection scratch, the next step's ids, the stop words, uniforms
     bool raw_blocks_ = false;  // ACE_MI_LM_RAW_BLOCKS at load: WF_GGML_RAW matrices are accepted and multiplied as blocks
     DevBuf raw_image_;         // the prefill's bf16 image of one raw-block matrix at a time (workspace, not weights)
+    DevBuf sc_xn_, sc_xh_, sc_work_;  // scoring: the scored rows after the final norm (f32, 16-bit), the kernel's scratch
     RopeTable rope_;  // positions 0..capacity-1
     int batch_ = 0, capacity_ = 0, len_ = 0;
     // Set by fanout(copies > 1), cleared by begin, reset and prefill: sequences g * shared_group_ + s hold sequence
@@ -544,6 +616,28 @@ ace_ggml_status ace_mi_lm_forward(ace_ggml_context* ctx, const int32_t* d_ids, c
         e->forward(d_ids, d_mask, n, d_logits, s);
     } catch (const std::exception& ex) {
         return set_error(ctx, ACE_GGML_ERR, std::string("lm forward failed: ") + ex.what());
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_lm_score(ace_ggml_context* ctx, const int32_t* d_ids, const int32_t* d_mask, int32_t n,
+                                int32_t score_from, float* d_logprob, int32_t* d_rank, float* d_logits, void* stream) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->lm) return set_error(ctx, ACE_GGML_ERR, "lm not loaded");
+    if (!d_ids || !d_logprob || !d_rank || n < 2) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm score: null pointer or n < 2");
+    if (score_from < 1 || score_from > n - 1)
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm score: score_from must be 1..n-1");
+    acemi::LmEngine* e = lm_of(ctx);
+    if (e->batch() <= 0) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm score: ace_mi_lm_begin was not called");
+    if (n > e->capacity()) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm score: exceeds the cache capacity");
+    if (e->len() > 0) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm score: a prefill needs an empty cache");
+    try {
+        bind_device(ctx);
+        acemi::gemm_splitk_check();
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+        e->score(d_ids, d_mask, n, score_from, d_logprob, d_rank, d_logits, s);
+    } catch (const std::exception& ex) {
+        return set_error(ctx, ACE_GGML_ERR, std::string("lm score failed: ") + ex.what());
     }
     return ACE_GGML_OK;
 }

@@ -442,6 +442,55 @@ ace_ggml_status ace_mi_kernel_lm_cache_fanout(int32_t layers, int32_t G, int32_t
     return ACE_GGML_OK;
 }
 
+ace_ggml_status ace_mi_kernel_lm_score(int32_t act_type, int32_t M, int32_t V, int32_t H, int32_t splits,
+                                       const uint16_t* x, const uint16_t* w, const int32_t* target, float* logprob,
+                                       int32_t* rank, int32_t* chain, int32_t reps, float* ms) {
+    using namespace acemi;
+    if ((act_type != 0 && act_type != 1) || M < 1 || V < 1 || H < 1 || splits < 0 || !x || !w || !target || !logprob ||
+        !rank || reps < 0 || (reps > 0 && !ms))
+        return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const ActType t = act_type == 1 ? ActType::F16 : ActType::BF16;
+        DevMem dx(x, (size_t)M * H * 2), dw(w, (size_t)V * H * 2), dt(target, (size_t)M * 4);
+        DevMem dlp(logprob, (size_t)M * 4), drk(rank, (size_t)M * 4), dwork(lm_score_work_floats(M, V, splits) * 4);
+        LmScoreArgs a;
+        a.x = dx.as<uint16_t>();
+        a.ldx = H;
+        a.w = dw.as<uint16_t>();
+        a.ldw = H;
+        a.M = M;
+        a.V = V;
+        a.H = H;
+        a.target = dt.as<int32_t>();
+        a.splits = splits;
+        a.work = dwork.as<float>();
+        a.logprob = dlp.as<float>();
+        a.rank = drk.as<int32_t>();
+        launch_lm_score(t, a, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        if (reps > 0) {  // the launch is warm: mean time of `reps` more, between two events on the null stream
+            hipEvent_t e0, e1;
+            ACEMI_HIP(hipEventCreate(&e0));
+            ACEMI_HIP(hipEventCreate(&e1));
+            ACEMI_HIP(hipEventRecord(e0, nullptr));
+            for (int i = 0; i < reps; ++i) launch_lm_score(t, a, nullptr);
+            ACEMI_HIP(hipEventRecord(e1, nullptr));
+            ACEMI_HIP(hipEventSynchronize(e1));
+            ACEMI_HIP(hipEventElapsedTime(ms, e0, e1));
+            *ms /= (float)reps;
+            (void)hipEventDestroy(e0);
+            (void)hipEventDestroy(e1);
+        }
+        dlp.to_host(logprob, (size_t)M * 4);
+        drk.to_host(rank, (size_t)M * 4);
+        if (chain) *chain = lm_score_chain(H);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_score: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
 namespace {
 // both attention entries: group_size 0 = launch_lm_attention, else launch_lm_attention_shared
 ace_ggml_status lm_attention_entry(const char* name, int32_t out_type, int32_t B, int32_t group_size, int32_t n_shared,

@@ -272,6 +272,19 @@ ACE_GGML_API ace_ggml_status ace_mi_lm_begin(ace_ggml_context* ctx, int32_t batc
  * cache; ACE_GGML_ERR "lm not loaded" before ace_mi_load_lm. */
 ACE_GGML_API ace_ggml_status ace_mi_lm_forward(ace_ggml_context* ctx, const int32_t* d_ids, const int32_t* d_mask,
                                                int32_t n, float* d_logits, void* stream);
+/* Teacher-forced scoring: the prefill of ace_mi_lm_forward (n > 1, empty cache, same d_ids / d_mask / padding rules)
+ * and, for every sequence b and position p in [score_from, n), the model's verdict on the token that is there:
+ *   d_logprob[b][p - score_from] = log softmax(logits at position p - 1)[ids[b][p]]                 (f32)
+ *   d_rank   [b][p - score_from] = number of ids whose logit at p - 1 is greater than that of ids[b][p], equal logits
+ *                                  ordered by id (0 = the argmax; rank < k <=> the token is in the top k)  (int32)
+ * One head product whose logits never reach memory (kernels/lm_score.hip); an out-of-range target id is clamped like
+ * every other id.  A head in block planes or raw blocks is expanded to its bf16 image for the call and released
+ * before it returns.  Afterwards the cache holds the n positions, as after the prefill; d_logits [batch][vocab], when
+ * not NULL, gets the last position's logits.  ACE_GGML_ERR_INVALID_ARG, cache unchanged: score_from outside
+ * [1, n - 1], n > capacity, a non-empty cache, no ace_mi_lm_begin; ACE_GGML_ERR "lm not loaded" before ace_mi_load_lm. */
+ACE_GGML_API ace_ggml_status ace_mi_lm_score(ace_ggml_context* ctx, const int32_t* d_ids, const int32_t* d_mask, int32_t n,
+                                             int32_t score_from, float* d_logprob, int32_t* d_rank, float* d_logits,
+                                             void* stream);
 /* Cache length back to 0 (batch and capacity kept). */
 ACE_GGML_API ace_ggml_status ace_mi_lm_reset(ace_ggml_context* ctx);
 

@@ -256,6 +256,16 @@ ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_cache_fanout(int32_t layers, int32
                                                            int32_t cap_src, int32_t cap_dst, int32_t n, uint16_t* k_src,
                                                            uint16_t* v_src, int32_t* mask_src, uint16_t* k_dst,
                                                            uint16_t* v_dst, int32_t* mask_dst);
+/* Teacher-forced scoring (kernels/lm_score.hip through launch_lm_score) on host arrays: x [M][H] and w [V][H] 16-bit
+ * words of act_type (0 bf16, 1 fp16), target [M] ids (clamped into [0, V)), splits = vocabulary runs per 64-row block
+ * (0 = automatic).  logprob [M] f32 and rank [M] int32 are written.  chain (may be NULL) receives the longest f32
+ * addition chain behind one logit.  reps > 0: after the first launch, `reps` more are timed between two events and
+ * *ms gets their mean (milliseconds).  INVALID_ARG: a null array or a non-positive size; ERR: what the launcher
+ * refuses (H % 32 != 0; message on stderr). */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_score(int32_t act_type, int32_t M, int32_t V, int32_t H, int32_t splits,
+                                                    const uint16_t* x, const uint16_t* w, const int32_t* target,
+                                                    float* logprob, int32_t* rank, int32_t* chain, int32_t reps,
+                                                    float* ms);
 /* ---- VAE conv kernels (csrc/kernels/vae.hip through launch_conv_gemm / launch_conv_out / launch_pack_f16 /
  * launch_to_f16 of csrc/kernels.h).  One launch each on host buffers, on a stream, blocking.
  * conv_gemm: the integer fields are those of ConvGemmArgs.  S [items][T_in][Cin] and W [N][taps * Cin] fp16 words;
