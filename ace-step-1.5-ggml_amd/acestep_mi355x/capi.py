@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = (
     "ace_ggml_generate_audio_style_lyric_timbre_simple", "ace_mi_reference_noise",
     "ace_mi_load_lm", "ace_mi_lm_get_info", "ace_mi_lm_begin", "ace_mi_lm_forward", "ace_mi_lm_reset",
     "ace_mi_lm_select", "ace_mi_lm_generate", "ace_mi_lm_fanout", "ace_mi_lm_uniforms",
-    "ace_mi_lm_score",
+    "ace_mi_lm_score", "ace_mi_lm_extend", "ace_mi_lm_truncate",
 )
 
 # Every symbol declared in include/acestep_mi355x_selftest.h: the TEST library (libacestep_mi355x_selftest.so = the
@@ -57,7 +57,7 @@ SELFTEST_SYMBOLS = ("ace_mi_kernel_gemm", "ace_mi_kernel_attention", "ace_mi_ker
                     "ace_mi_kernel_attn_policy", "ace_mi_attn_plan", "ace_mi_attn_plan_block", "ace_mi_attn_plan_tiles",
                     "ace_mi_kernel_lm_skinny", "ace_mi_kernel_lm_embed", "ace_mi_kernel_lm_qkv_post",
                     "ace_mi_kernel_lm_prefill_kv", "ace_mi_kernel_lm_attention", "ace_mi_kernel_lm_attention_shared",
-                    "ace_mi_kernel_lm_skinny_q",
+                    "ace_mi_kernel_lm_attention_chunk", "ace_mi_kernel_lm_skinny_q",
                     "ace_mi_kernel_lm_embed_q", "ace_mi_kernel_lm_skinny_blocks", "ace_mi_kernel_lm_embed_blocks",
                     "ace_mi_kernel_lm_select", "ace_mi_kernel_lm_cache_fanout", "ace_mi_kernel_lm_score",
                     "ace_mi_kernel_conv_gemm", "ace_mi_kernel_conv_out", "ace_mi_kernel_pack_f16",
@@ -297,6 +297,10 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
         lib.ace_mi_lm_uniforms.restype = ctypes.c_int
         lib.ace_mi_lm_score.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
         lib.ace_mi_lm_score.restype = ctypes.c_int
+        lib.ace_mi_lm_extend.argtypes = [vp, vp, vp, i32, i32, vp, vp, vp, vp]
+        lib.ace_mi_lm_extend.restype = ctypes.c_int
+        lib.ace_mi_lm_truncate.argtypes = [vp, i32]
+        lib.ace_mi_lm_truncate.restype = ctypes.c_int
     if path is None:
         _LIB = lib
     return lib
@@ -606,6 +610,47 @@ class GGMLCAPIBridge:
                                           int(score_from), logprob.data_ptr(), rank.data_ptr(), None, stream or None)
             self._ensure_ok(st, "ace_mi_lm_score")
         return logprob, rank
+
+    def lm_truncate(self, length: int) -> None:
+        """Cache length back to `length` in [0, cache_len] (ace_mi_lm_truncate)."""
+        self._ensure_ok(self.lib.ace_mi_lm_truncate(self.ctx, int(length)), "ace_mi_lm_truncate")
+
+    def lm_extend(self, input_ids, attention_mask=None, score_from=None, want_logits=None):
+        """Append the chunk input_ids [B, n] to the filled cache (ace_mi_lm_extend).  score_from None: returns the last
+        position's logits, f32 [B, vocab].  score_from in 1 .. n-1: returns (logprob f32 [B, n - score_from], rank
+        int32 [B, n - score_from]) for the chunk's positions score_from .. n-1, as lm_score does for a prefill -- and
+        (logprob, rank, logits) when want_logits.  Tensors and stream rules as in lm_forward."""
+        import torch
+        from .hook import _OrderedCall
+        ids = input_ids.detach().to(torch.int32).contiguous()
+        if ids.dim() != 2:
+            raise ValueError("lm_extend: input_ids must be [B, n]")
+        dev = ids.device
+        am = None
+        if attention_mask is not None:
+            am = (attention_mask.detach().to(dev) != 0).to(torch.int32).contiguous()
+            if am.shape != ids.shape:
+                raise ValueError("lm_extend: attention_mask must cover exactly the appended columns")
+        B, n = ids.shape
+        scoring = score_from is not None
+        logits = logprob = rank = None
+        if want_logits or (want_logits is None and not scoring):
+            if getattr(self, "_lm_vocab", None) is None:
+                self._lm_vocab = self.lm_info()["vocab_size"]
+            logits = torch.empty((B, self._lm_vocab), dtype=torch.float32, device=dev)
+        if scoring:
+            T = max(n - int(score_from), 0)
+            logprob = torch.empty((B, T), dtype=torch.float32, device=dev)
+            rank = torch.empty((B, T), dtype=torch.int32, device=dev)
+        with _OrderedCall(self, dev) as stream:
+            st = self.lib.ace_mi_lm_extend(self.ctx, ids.data_ptr(), am.data_ptr() if am is not None else None, n,
+                                           int(score_from) if scoring else 0,
+                                           logprob.data_ptr() if scoring else None, rank.data_ptr() if scoring else None,
+                                           logits.data_ptr() if logits is not None else None, stream or None)
+            self._ensure_ok(st, "ace_mi_lm_extend")
+        if not scoring:
+            return logits
+        return (logprob, rank, logits) if logits is not None else (logprob, rank)
 
     def _lm_sample_params(self, dev, allowed_ids=None, stop_id=-1, min_tokens=0, cfg_scale=1.0, pre_temperature=0.0,
                           temperature=1.0, top_k=0, top_p=1.0, repetition_penalty=1.0, seed=0):
@@ -1236,6 +1281,7 @@ def _bind_lm_kernels(lib):
     lib.ace_mi_kernel_lm_prefill_kv.argtypes = [i32] * 6 + [f32, fp, fp, fp, fp, ip, u16p, u16p, ip]
     lib.ace_mi_kernel_lm_attention.argtypes = [i32] * 6 + [f32, fp, u16p, u16p, ip, u16p]
     lib.ace_mi_kernel_lm_attention_shared.argtypes = [i32] * 8 + [f32, fp, u16p, u16p, ip, u16p]
+    lib.ace_mi_kernel_lm_attention_chunk.argtypes = [i32] * 7 + [f32, fp, u16p, u16p, ip, u16p]
     u8p = ctypes.POINTER(ctypes.c_uint8)
     lib.ace_mi_kernel_lm_skinny_q.argtypes = [i32] * 8 + [u16p, u8p, fp, u16p, ip]
     lib.ace_mi_kernel_lm_embed_q.argtypes = [i32] * 4 + [u8p, ip, fp]
@@ -1483,6 +1529,22 @@ def kernel_lm_attention_shared(q: np.ndarray, k_cache: np.ndarray, v_cache: np.n
                                                kc.shape[1], kc.shape[2], nk, n_shared, scale, _fptr(qq), _u16ptr(kc),
                                                _u16ptr(vc), _iptr(km), _u16ptr(out))
     _lm_status("attention_shared", st)
+    return out
+
+
+def kernel_lm_attention_chunk(q: np.ndarray, k_cache: np.ndarray, v_cache: np.ndarray, key_mask: np.ndarray, past: int,
+                              scale: float, out_type: int = 0, lib=None) -> np.ndarray:
+    """launch_lm_attention_chunk: q [B][n][hq][128] f32 for the tokens at slots past .. past + n - 1, caches and
+    key_mask as kernel_lm_attention takes them -> uint16 [B][n][hq][128] words of out_type (0 bf16, 1 fp16)."""
+    lib = _lm_lib(lib)
+    qq = np.ascontiguousarray(q, dtype=np.float32)
+    kc, vc = (np.ascontiguousarray(a, dtype=np.uint16) for a in (k_cache, v_cache))
+    km = np.ascontiguousarray(key_mask, dtype=np.int32)
+    B, n, hq = qq.shape[0], qq.shape[1], qq.shape[2]
+    out = np.full((B, n, hq, 128), 0x7fff, dtype=np.uint16)
+    st = lib.ace_mi_kernel_lm_attention_chunk(out_type, B, hq, kc.shape[1], kc.shape[2], past, n, scale, _fptr(qq),
+                                              _u16ptr(kc), _u16ptr(vc), _iptr(km), _u16ptr(out))
+    _lm_status("attention_chunk", st)
     return out
 
 

@@ -469,6 +469,37 @@ class EngineCausalLM:
         self._live.length += n
         return out
 
+    def score_after_prompt(self, input_ids, attention_mask, prompt_len: int, reserve: int = 1024):
+        """score(input_ids, attention_mask, prompt_len) with the prompt's prefill reused between calls: the first
+        prompt_len columns are prefilled once (bridge.lm_forward, a cache of prompt_len + max(reserve, target)
+        positions) and remembered by their token ids and batch; while the next call's prompt is the same and the
+        cache is still the live one, only [last prompt token] + target runs, as a chunk on the cache cut back to
+        prompt_len - 1 (bridge.lm_truncate + bridge.lm_extend, score_from = 1).  The chunk reads K and V from the fp16
+        cache where the prefill reads hi + lo pairs: the scores agree with score()'s to the last bits, not bit for
+        bit.  A prompt shorter than 2 tokens goes through score()."""
+        if input_ids is None or input_ids.dim() != 2:
+            raise ValueError("input_ids must be a [B, n] tensor")
+        B, n, P = int(input_ids.shape[0]), int(input_ids.shape[1]), int(prompt_len)
+        if P < 2 or P >= n:
+            return self.score(input_ids, attention_mask, prompt_len)
+        key = (B, tuple(input_ids[:, :P].reshape(-1).tolist()),
+               None if attention_mask is None else tuple(attention_mask[:, :P].reshape(-1).tolist()))
+        kept = getattr(self, "_score_prompt", None)
+        if kept is None or kept[0] != key or kept[1] is not self._live or n > kept[2]:
+            cap = P + max(int(reserve), n - P)
+            self.bridge.lm_begin(B, cap)
+            self._serial += 1
+            self._live = _LmCacheHandle(self._serial)
+            self._last_logits = None
+            self.bridge.lm_forward(input_ids[:, :P], None if attention_mask is None else attention_mask[:, :P])
+            self._score_prompt = (key, self._live, cap)
+        self.bridge.lm_truncate(P - 1)
+        out = self.bridge.lm_extend(input_ids[:, P - 1:], None if attention_mask is None else attention_mask[:, P - 1:],
+                                    score_from=1)
+        self._live.length = n
+        self._last_logits = None
+        return out
+
     def generate_codes(self, n_codes: int, allowed_ids, eos_id: int, cfg_scale: float = 1.0, codes_temperature=None,
                        temperature: float = 1.0, top_k=None, top_p=None, repetition_penalty: float = 1.0,
                        prompt_ids=None, seed: int = 0, uniforms=None):
@@ -715,11 +746,12 @@ def _run_pt_fanout(handler, prompts, temperature, cfg_scale, negative_prompt, to
     return texts
 
 
-def _engine_target_scores(llm_handler, formatted_prompt: str, target_text: str):
+def _engine_target_scores(llm_handler, formatted_prompt: str, target_text: str, reuse_prompt: bool = False):
     """(logprob, rank) of the target's tokens given the prompt, 1-D CPU tensors, or None for an empty target: the
     tokenisation of the reference's _get_logits_and_target_for_scoring (acestep/test_time_scaling.py:141-155: the prompt
     alone for its length, then prompt + target in one piece), scored by EngineCausalLM.score instead of a forward that
-    returns every position's logits."""
+    returns every position's logits.  reuse_prompt: through EngineCausalLM.score_after_prompt, which prefills a prompt
+    once for all the targets scored against it in a row."""
     import torch
     tok = llm_handler.llm_tokenizer
     prompt_len = int(tok(formatted_prompt, return_tensors="pt", add_special_tokens=True)["input_ids"].shape[1])
@@ -732,17 +764,18 @@ def _engine_target_scores(llm_handler, formatted_prompt: str, target_text: str):
     if dev is None or str(dev) == "auto":
         dev = model.device
     with torch.no_grad():
-        logprob, rank = model.score(ids.to(dev), full["attention_mask"].to(dev), prompt_len)
+        score = model.score_after_prompt if reuse_prompt else model.score
+        logprob, rank = score(ids.to(dev), full["attention_mask"].to(dev), prompt_len)
     return logprob[0].cpu(), rank[0].cpu()
 
 
-def _install_scoring(scoring_module) -> None:
+def _install_scoring(scoring_module, reuse_prompt: bool = False) -> None:
     def log_prob_mi355x(llm_handler, formatted_prompt, target_text, temperature=1.0):
-        got = _engine_target_scores(llm_handler, formatted_prompt, target_text)
+        got = _engine_target_scores(llm_handler, formatted_prompt, target_text, reuse_prompt)
         return float("-inf") if got is None else got[0].mean().item()
 
     def topk_recall_mi355x(llm_handler, formatted_prompt, target_text, topk=10):
-        got = _engine_target_scores(llm_handler, formatted_prompt, target_text)
+        got = _engine_target_scores(llm_handler, formatted_prompt, target_text, reuse_prompt)
         if got is None:
             return 0.0, {}
         rank = got[1].tolist()
@@ -755,7 +788,7 @@ def _install_scoring(scoring_module) -> None:
 
 
 def install_lm_backend(llm_handler: Any, bridge, max_new_tokens: int = 4096, device_codes: bool = False,
-                       batch_codes: bool = False, scoring_module=None) -> None:
+                       batch_codes: bool = False, scoring_module=None, reuse_score_prompt: bool = False) -> None:
     """Point the reference LLM handler's `pt` backend at the engine: `llm_handler.llm` becomes an EngineCausalLM over
     the LM that `bridge.load_lm` loaded (needs no `transformers`).
 
@@ -780,11 +813,18 @@ def install_lm_backend(llm_handler: Any, bridge, max_new_tokens: int = 4096, dev
     position's), so with the engine installed its scores are empty.  When the module is given, its `_calculate_log_prob`
     and `_calculate_topk_recall` (same signatures and return values, so `calculate_pmi_score_per_condition` runs as it
     is) are replaced by functions that score the target with EngineCausalLM.score: one prefill, one fused head /
-    log-softmax / rank kernel, no [n, vocab] logits."""
+    log-softmax / rank kernel, no [n, vocab] logits.
+
+    reuse_score_prompt=True (with a scoring_module): the wrappers remember the token ids and batch of the prompt they
+    prefilled last; a call with the same prompt runs only [last prompt token] + target as a chunk on that cache
+    (EngineCausalLM.score_after_prompt: lm_truncate + lm_extend), any other prompt is prefilled afresh.  The auto score's
+    up to eight calls per item share one formatted_prompt, so they cost one prompt prefill.  Off by default: the chunk
+    reads K and V from the fp16 cache where the prefill reads hi + lo pairs, so log-probabilities differ in the last
+    bits from the default path's."""
     if batch_codes and not device_codes:
         raise ValueError("install_lm_backend: batch_codes=True needs device_codes=True")
     if scoring_module is not None:
-        _install_scoring(scoring_module)
+        _install_scoring(scoring_module, bool(reuse_score_prompt))
     device = getattr(llm_handler, "device", None)
     if device is None or str(device) in ("auto", "cpu"):
         device = "cuda"

@@ -518,6 +518,10 @@ void launch_lm_qkv_post(const LmQkvPostArgs& a, int B, hipStream_t s);
 // prefill: rows b*n + t of qkv -> slots t < n; mask [B][n] or null; the q|k|v values of a padding row (mask 0) are
 // zeroed in place and in the cache (q_out, pos and mask_new unused)
 void launch_lm_prefill_kv(const LmQkvPostArgs& a, int B, int n, const int32_t* mask, hipStream_t s);
+// a chunk onto a filled cache: rows b*n + t of qkv -> slots a.pos + t (K normed and rotated at position a.pos + t),
+// key_mask[b][a.pos + t] from mask [B][n] (null = valid), padding rows zeroed as launch_lm_prefill_kv does; and Q, normed
+// and rotated like launch_lm_qkv_post's, into a.q_out [B][n][hq][128] f32.  n = 1, valid rows: launch_lm_qkv_post's bytes.
+void launch_lm_chunk_kv(const LmQkvPostArgs& a, int B, int n, const int32_t* mask, hipStream_t s);
 struct LmAttnArgs {
     const float* q = nullptr;  // [B][hq][128] f32
     const uint16_t* k_cache = nullptr;
@@ -557,6 +561,36 @@ inline int lm_attn_shared_check(const LmAttnArgs& a, int B, int rep) {
                 "lm_attention_shared: items per workgroup must be 2, 4 or 8 and items x GQA ratio at most 16");
     return items;
 }
+
+// the join of launch_lm_attention's records part [rows][hq][n_split][130] in ascending range order -> out [rows][hq*128]
+void launch_lm_attn_merge(ActType out_t, const float* part, int rows, int hq, int n_split, uint16_t* out, hipStream_t s);
+// Chunk attention (kernels/lm_attn_chunk.hip): n query tokens per sequence at slots past .. past + n - 1, whose K and V
+// are already in the cache.  Row (b, t, head) attends the keys j <= past + t with key_mask[b][j] != 0; a masked key's K
+// and V never reach the result, slots >= past + n are not read, a row without a visible key is +0 in every word.
+struct LmAttnChunkArgs {
+    const float* q = nullptr;  // [B][n][hq][128] f32, normalised and rotated
+    const uint16_t* k_cache = nullptr;
+    const uint16_t* v_cache = nullptr;
+    const int32_t* key_mask = nullptr;
+    int hkv = 0, capacity = 0;
+    int past = 0, n = 0;
+    float scale = 0.f;
+    uint16_t* out = nullptr;  // [B*n][hq*128] in the act type
+    float* part = nullptr;    // lm_attn_chunk_part_floats() floats when past + n > LM_SPLIT_KEYS
+};
+constexpr int LM_CHUNK_ROWS = 32;  // query rows (token-major over the GQA group) of one workgroup
+size_t lm_attn_chunk_part_floats(int B, int n, int hq, int nk);
+// the launcher's conditions; returns the GQA ratio
+inline int lm_attn_chunk_check(const LmAttnChunkArgs& a, int B, int hq) {
+    ACEMI_CHECK(B >= 1 && B <= LM_MAX_BATCH && a.hkv >= 1 && hq >= 1 && hq % a.hkv == 0 && a.n >= 1 && a.past >= 0 &&
+                    (int64_t)a.past + a.n <= a.capacity && a.q && a.k_cache && a.v_cache && a.key_mask && a.out,
+                "lm_attention_chunk: bad arguments");
+    const int rep = hq / a.hkv;
+    ACEMI_CHECK(rep == 1 || rep == 2 || rep == 4, "lm_attention_chunk: GQA ratio must be 1, 2 or 4");
+    ACEMI_CHECK((int64_t)B * a.n <= 65535 && (int64_t)B * a.hkv <= 65535, "lm_attention_chunk: too many rows for one launch");
+    return rep;
+}
+void launch_lm_attention_chunk(ActType out_t, const LmAttnChunkArgs& a, int B, int hq, hipStream_t s);
 
 // ------------------------------------------------------------ LM cache fan-out (kernels/lm_fanout.hip)
 // A prefilled cache of G = 1 or 2 sequences re-laid for G * S sequences: destination sequence g * S + s is a bit copy of

@@ -12,6 +12,8 @@
 //   lm_prefill_kv_kernel the same K / V append for every row of a prefill (from the QKV GEMM's f32 output); rows of
 //                       padding tokens (mask 0) are zeroed in the GEMM output and in the cache, so that a
 //                       left-padded prompt never feeds a non-finite value into another row's attention.
+//   lm_chunk_kv_kernel  the same append for a chunk of rows onto a filled cache (slot pos + t), with the rows' Q (norm,
+//                       RoPE) kept in f32 for kernels/lm_attn_chunk.hip.
 //   lm_attn_kernel      one workgroup per (key range, kv head, sequence): the hq / hkv query heads of the kv head
 //                       share one read of K and V; scores, f32 softmax and P.V over up to LM_SPLIT_KEYS keys.
 //                       More keys: one workgroup per range of LM_SPLIT_KEYS writes (m, l, unnormalised O) and
@@ -225,6 +227,36 @@ __global__ void __launch_bounds__(64) lm_prefill_kv_kernel(LmQkvPostArgs a, int 
     float v0 = valid ? src[lane] : 0.f, v1 = valid ? src[64 + lane] : 0.f;
     if (is_k && valid) norm_rope(v0, v1, a.k_norm, a.rope_cos + (int64_t)t * 64, a.rope_sin + (int64_t)t * 64, a.eps, lane);
     uint16_t* dst = (is_k ? a.k_cache : a.v_cache) + (((int64_t)b * a.hkv + kh) * a.capacity + t) * LM_D;
+    dst[lane] = f16_sat(v0);
+    dst[64 + lane] = f16_sat(v1);
+}
+
+// grid (hq + 2 hkv, n, B): row m = b * n + t of a chunk's QKV output -> slot a.pos + t of a filled cache, Q kept
+__global__ void __launch_bounds__(64) lm_chunk_kv_kernel(LmQkvPostArgs a, int n, const int32_t* __restrict__ mask) {
+    const int head = blockIdx.x, t = blockIdx.y, b = blockIdx.z, lane = threadIdx.x;
+    const int64_t m = (int64_t)b * n + t;
+    const int slot = a.pos + t;
+    const bool valid = mask ? mask[m] != 0 : true;
+    float* src = const_cast<float*>(a.qkv) + m * a.ld + (int64_t)head * LM_D;
+    if (!valid) {  // as in the prefill: a padding row carries nothing into any other row
+        src[lane] = 0.f;
+        src[64 + lane] = 0.f;
+    }
+    float v0 = valid ? src[lane] : 0.f, v1 = valid ? src[64 + lane] : 0.f;
+    const float* cs = a.rope_cos + (int64_t)slot * 64;
+    const float* sn = a.rope_sin + (int64_t)slot * 64;
+    if (head < a.hq) {
+        if (valid) norm_rope(v0, v1, a.q_norm, cs, sn, a.eps, lane);
+        float* q = a.q_out + (m * a.hq + head) * LM_D;
+        q[lane] = v0;
+        q[64 + lane] = v1;
+        if (head == 0 && lane == 0) a.key_mask[(int64_t)b * a.capacity + slot] = valid ? 1 : 0;
+        return;
+    }
+    const bool is_k = head < a.hq + a.hkv;
+    const int kh = is_k ? head - a.hq : head - a.hq - a.hkv;
+    if (is_k && valid) norm_rope(v0, v1, a.k_norm, cs, sn, a.eps, lane);
+    uint16_t* dst = (is_k ? a.k_cache : a.v_cache) + (((int64_t)b * a.hkv + kh) * a.capacity + slot) * LM_D;
     dst[lane] = f16_sat(v0);
     dst[64 + lane] = f16_sat(v1);
 }
@@ -473,6 +505,14 @@ void launch_lm_prefill_kv(const LmQkvPostArgs& a, int B, int n, const int32_t* m
     ACEMI_HIP(hipGetLastError());
 }
 
+void launch_lm_chunk_kv(const LmQkvPostArgs& a, int B, int n, const int32_t* mask, hipStream_t s) {
+    check_post(a, B);
+    ACEMI_CHECK(n >= 1 && a.pos >= 0 && (int64_t)a.pos + n <= a.capacity && n <= 65535 && a.q_out,
+                "lm_chunk_kv: rows outside the cache");
+    hipLaunchKernelGGL(lm_chunk_kv_kernel, dim3(a.hq + 2 * a.hkv, n, B), dim3(64), 0, s, a, n, mask);
+    ACEMI_HIP(hipGetLastError());
+}
+
 size_t lm_attn_part_floats(int B, int hq, int nk) {
     return (size_t)B * hq * ceil_div(nk, LM_SPLIT_KEYS) * (LM_D + 2);
 }
@@ -494,6 +534,15 @@ static void lm_attn_merge(bool f16, const LmAttnArgs& a, int B, int hq, hipStrea
         hipLaunchKernelGGL(lm_attn_merge_kernel<true>, dim3(hq, B), dim3(128), 0, s, a.part, hq, a.n_split, a.out);
     else
         hipLaunchKernelGGL(lm_attn_merge_kernel<false>, dim3(hq, B), dim3(128), 0, s, a.part, hq, a.n_split, a.out);
+    ACEMI_HIP(hipGetLastError());
+}
+
+void launch_lm_attn_merge(ActType out_t, const float* part, int rows, int hq, int n_split, uint16_t* out, hipStream_t s) {
+    ACEMI_CHECK(part && out && rows >= 1 && rows <= 65535 && hq >= 1 && n_split >= 1, "lm_attn_merge: bad arguments");
+    if (out_t == ActType::F16)
+        hipLaunchKernelGGL(lm_attn_merge_kernel<true>, dim3(hq, rows), dim3(128), 0, s, part, hq, n_split, out);
+    else
+        hipLaunchKernelGGL(lm_attn_merge_kernel<false>, dim3(hq, rows), dim3(128), 0, s, part, hq, n_split, out);
     ACEMI_HIP(hipGetLastError());
 }
 

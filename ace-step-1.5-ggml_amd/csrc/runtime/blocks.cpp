@@ -23,7 +23,7 @@ float* BlockRunner::x(int64_t rows, int H) {
 
 void BlockRunner::run(const BlockShape& sh, const std::vector<DevLayer>& layers, int n_layers, ActType at, int B,
                       int n, const int32_t* key_mask, bool causal, hipStream_t s, const AfterQkv* after_qkv,
-                      const Operand* operand) {
+                      const Operand* operand, const Attention* attention) {
     const int H = sh.hidden, D = sh.head_dim, I = sh.intermediate;
     ACEMI_CHECK(B >= 1 && n >= 1 && D == 128, "blocks: bad shape");
     ACEMI_CHECK(n_layers >= 0 && n_layers <= (int)layers.size(), "blocks: layer count");
@@ -38,18 +38,20 @@ void BlockRunner::run(const BlockShape& sh, const std::vector<DevLayer>& layers,
     ensure(attn_, (size_t)M * qd * 2);
     ensure(act2_, (size_t)M * std::max(I, 1) * 2);
     ensure(qkv_, (size_t)M * (qd + 2 * kd) * 4);
-    ensure(qh_, (size_t)2 * q_plane * 2);
-    ensure(kh_, (size_t)2 * k_plane * 2);
-    ensure(vt_, (size_t)2 * k_plane * 2);
-    ensure(kbias_, (size_t)B * Npad * 4);
-    rope_.ensure(n, D, sh.rope_theta, s);
+    if (!attention) {
+        ensure(qh_, (size_t)2 * q_plane * 2);
+        ensure(kh_, (size_t)2 * k_plane * 2);
+        ensure(vt_, (size_t)2 * k_plane * 2);
+        ensure(kbias_, (size_t)B * Npad * 4);
+        rope_.ensure(n, D, sh.rope_theta, s);
+    }
     float* x = get<float>(x_);
     uint16_t* act = get<uint16_t>(act_);
     uint16_t* attn = get<uint16_t>(attn_);
     uint16_t* act2 = get<uint16_t>(act2_);
     float* qkv = get<float>(qkv_);
     uint16_t *qh = get<uint16_t>(qh_), *kh = get<uint16_t>(kh_), *vt = get<uint16_t>(vt_);
-    launch_key_bias(key_mask, B, n, 1, n, Npad, get<float>(kbias_), s);
+    if (!attention) launch_key_bias(key_mask, B, n, 1, n, Npad, get<float>(kbias_), s);
     const float* kbias = key_mask ? get<float>(kbias_) : nullptr;  // padding keys are masked in-kernel
     const auto view = [&](const DevWeight& w) { return operand ? (*operand)(w) : w.view(); };
     for (int li = 0; li < n_layers; ++li) {
@@ -57,13 +59,17 @@ void BlockRunner::run(const BlockShape& sh, const std::vector<DevLayer>& layers,
         launch_rmsnorm_mod(at, x, M, H, ly.self_norm, nullptr, nullptr, 0, n, sh.eps, act, s);
         launch_gemm(act, H, view(ly.w_qkv), M, qd + 2 * kd, H, epi_store_f32(qkv, qd + 2 * kd), s);
         if (after_qkv) (*after_qkv)(li, qkv, qd + 2 * kd);
-        launch_attn_prep(self_prep(dims, planes, qkv, qd + 2 * kd, ly.sq_norm, ly.sk_norm, rope_.cos(), rope_.sin(), qh,
-                                   kh, vt),
-                         s);
-        launch_attention(at,
-                         attn_args(dims, planes, qh, kh, vt, kbias, n, Npad, dims.k_plane(),
-                                   ly.sliding ? std::max(sh.sliding_window, 0) : 0, causal, nullptr, attn),
-                         s);
+        if (attention) {
+            (*attention)(li, qkv, qd + 2 * kd, attn);
+        } else {
+            launch_attn_prep(self_prep(dims, planes, qkv, qd + 2 * kd, ly.sq_norm, ly.sk_norm, rope_.cos(), rope_.sin(),
+                                       qh, kh, vt),
+                             s);
+            launch_attention(at,
+                             attn_args(dims, planes, qh, kh, vt, kbias, n, Npad, dims.k_plane(),
+                                       ly.sliding ? std::max(sh.sliding_window, 0) : 0, causal, nullptr, attn),
+                             s);
+        }
         launch_gemm(attn, qd, view(ly.w_o), M, H, qd, epi_resid(x, H), s);  // h = x + o_proj(attn)
         launch_rmsnorm_mod(at, x, M, H, ly.mlp_norm, nullptr, nullptr, 0, n, sh.eps, act, s);
         launch_gemm(act, H, view(ly.w_gu), M, 2 * I, H, epi_swiglu(act2, I), s);

@@ -40,9 +40,14 @@ class BlockRunner {
     // reads, and what it enqueues on s runs before that GEMM (the causal LM's raw-block mode expands a WF_GGML_RAW
     // matrix into one reused bf16 scratch here: stream order keeps a GEMM ahead of the next expansion)
     using Operand = std::function<WeightView(const DevWeight& w)>;
+    // attention (optional): replaces the layer's attention prep and flash attention.  Called with the same qkv rows
+    // after after_qkv; what it enqueues on s must leave the layer's attention output [B*n][hq*head_dim] in the act
+    // type at `out` (the causal LM's chunk onto a filled cache attends to its KV cache here, runtime/lm.cpp).  The
+    // runner then neither builds a key bias nor allocates the attention planes; key_mask and causal are the hook's.
+    using Attention = std::function<void(int li, float* qkv, int ld, uint16_t* out)>;
     void run(const BlockShape& sh, const std::vector<DevLayer>& layers, int n_layers, ActType act, int B, int n,
              const int32_t* key_mask, bool causal, hipStream_t s, const AfterQkv* after_qkv = nullptr,
-             const Operand* operand = nullptr);
+             const Operand* operand = nullptr, const Attention* attention = nullptr);
     // out = RMSNorm(x) * w (w null: a plain copy) for all B*n rows, or each item's token 0 when first_only
     void finish(const BlockShape& sh, const float* w, int B, int n, bool first_only, float* out, hipStream_t s);
 

@@ -4,6 +4,10 @@
 //
 //   prefill (n > 1, empty cache)  the text encoder's path: BlockRunner (MFMA GEMMs, causal flash attention, key mask);
 //                                 its after-QKV hook stores every layer's post-norm, post-RoPE K and V into the cache.
+//   chunk (ace_mi_lm_extend)      n >= 1 tokens onto a filled cache: the prefill's BlockRunner walk (the same GEMMs and
+//                                 rounding points) with its attention replaced by kernels/lm_decode.hip's chunk
+//                                 append (K, V into the cache, Q kept in f32) and kernels/lm_attn_chunk.hip, which
+//                                 reads K and V from the cache as the decode step does.
 //   decode step (n == 1)          kernels/lm_decode.hip: skinny products over the same fused matrices DevLayer holds,
 //                                 QKV post-processing, decode attention over the cache.  A matrix in ggml block planes
 //                                 (a GGUF checkpoint's Q8_0 / Q4_K / Q6_K tensors) goes through kernels/lm_decode_q.hip,
@@ -24,6 +28,7 @@
 #include <random>
 #include <vector>
 
+#include "../kernels/lm_attn_chunk_host.h"   // empty under hipcc; the host build's launch_lm_chunk_kv / launch_lm_attention_chunk
 #include "../kernels/lm_attn_shared_host.h"  // empty under hipcc; the host build's launch_lm_attention_shared
 #include "../kernels/lm_decode_blocks_host.h"  // empty under hipcc; the host build's launch_lm_skinny_blocks / _embed_blocks
 #include "../kernels/lm_decode_q_host.h"  // empty under hipcc; the host build's launch_lm_skinny_q / launch_lm_embed_q
@@ -181,6 +186,59 @@ class LmEngine {
         const ScoreOut out{score_from, d_logprob, d_rank};
         prefill(d_ids, d_mask, n, d_logits, s, &out);
         len_ += n;
+    }
+
+    // A chunk of n >= 1 tokens per sequence onto the filled cache (ace_mi_lm_extend): positions len_ .. len_ + n - 1.
+    // score_from > 0: rows score_from-1 .. n-2 of the chunk are scored against its ids score_from .. n-1, as score()
+    // does for a prefill.  The caller has checked the arguments; d_logits may be null.
+    void extend(const int32_t* d_ids, const int32_t* d_mask, int n, int score_from, float* d_logprob, int32_t* d_rank,
+                float* d_logits, hipStream_t s) {
+        const TextConfig& c = model_.cfg;
+        const BlockShape sh = shape();
+        const int M = batch_ * n, past = len_;
+        if (past < shared_len_) {  // the chunk overwrites copied positions
+            shared_len_ = 0;
+            shared_group_ = 1;
+        }
+        const int nk = past + n;
+        q_chunk_.ensure((size_t)M * c.hq * c.head_dim * 4);
+        if (nk > LM_SPLIT_KEYS) part_chunk_.ensure(lm_attn_chunk_part_floats(batch_, n, c.hq, nk) * 4);
+        float* x = blocks_.x(M, sh.hidden);
+        embed(d_ids, M, x, s);
+        const BlockRunner::Attention attend = [&](int li, float* qkv, int ld, uint16_t* out) {
+            LmQkvPostArgs pa = post_args(li, qkv, ld);
+            pa.q_out = q_chunk_.as<float>();
+            pa.pos = past;
+            launch_lm_chunk_kv(pa, batch_, n, d_mask, s);
+            LmAttnChunkArgs aa;
+            aa.q = pa.q_out;
+            aa.k_cache = pa.k_cache;
+            aa.v_cache = pa.v_cache;
+            aa.key_mask = pa.key_mask;
+            aa.hkv = c.hkv;
+            aa.capacity = capacity_;
+            aa.past = past;
+            aa.n = n;
+            aa.scale = 1.0f / std::sqrt((float)c.head_dim);
+            aa.out = out;
+            aa.part = part_chunk_.as<float>();
+            launch_lm_attention_chunk(model_.act, aa, batch_, c.hq, s);
+        };
+        const BlockRunner::Operand expand = expander(s);
+        blocks_.run(sh, model_.layers, c.layers, model_.act, batch_, n, d_mask, true, s, nullptr,
+                    raw_blocks_ ? &expand : nullptr, &attend);
+        if (d_logits) head(x + (size_t)(n - 1) * sh.hidden, n, d_logits, s);
+        if (score_from > 0) score_rows(x, d_ids, n, ScoreOut{score_from, d_logprob, d_rank}, s);
+        len_ += n;
+    }
+
+    // the cache length back to `len` <= len_ (ace_mi_lm_truncate); batch and capacity stay
+    void truncate(int len) {
+        len_ = len;
+        if (len < shared_len_) {
+            shared_len_ = 0;
+            shared_group_ = 1;
+        }
     }
 
     // The selection arguments shared by select() and generate(); `why` names what is wrong with them, if anything.
@@ -433,6 +491,22 @@ class LmEngine {
         if (scratch) ACEMI_HIP(hipStreamSynchronize(s));  // the sweep has read the image: it may go
     }
 
+    // a raw-block matrix: its bf16 image (the default mode's resident one, bit for bit) into the scratch, on s
+    BlockRunner::Operand expander(hipStream_t s) {
+        return [this, s](const DevWeight& w) {
+            if (w.fmt != WF_GGML_RAW) return w.view();
+            uint16_t* img = raw_image_.as<uint16_t>();
+            std::vector<DequantBlocksJob> jobs;
+            for (const BlockSeg& g : w.segs) jobs.push_back(DequantBlocksJob{g, w.cols, w.cols, img});
+            launch_dequant_blocks(jobs.data(), (int)jobs.size(), s);
+            WeightView v;
+            v.fmt = WF_BF16;
+            v.q = img;
+            v.ld = w.cols;
+            return v;
+        };
+    }
+
     void prefill(const int32_t* d_ids, const int32_t* d_mask, int n, float* d_logits, hipStream_t s,
                  const ScoreOut* score = nullptr) {
         const TextConfig& c = model_.cfg;
@@ -445,19 +519,7 @@ class LmEngine {
         const BlockRunner::AfterQkv fill = [&](int li, float* qkv, int ld) {
             launch_lm_prefill_kv(post_args(li, qkv, ld), batch_, n, d_mask, s);
         };
-        // a raw-block matrix: its bf16 image (the default mode's resident one, bit for bit) into the scratch, on s
-        const BlockRunner::Operand expand = [&](const DevWeight& w) {
-            if (w.fmt != WF_GGML_RAW) return w.view();
-            uint16_t* img = raw_image_.as<uint16_t>();
-            std::vector<DequantBlocksJob> jobs;
-            for (const BlockSeg& g : w.segs) jobs.push_back(DequantBlocksJob{g, w.cols, w.cols, img});
-            launch_dequant_blocks(jobs.data(), (int)jobs.size(), s);
-            WeightView v;
-            v.fmt = WF_BF16;
-            v.q = img;
-            v.ld = w.cols;
-            return v;
-        };
+        const BlockRunner::Operand expand = expander(s);
         blocks_.run(sh, model_.layers, c.layers, model_.act, batch_, n, d_mask, true, s, &fill, raw_blocks_ ? &expand : nullptr);
         if (d_logits) head(x + (size_t)(n - 1) * sh.hidden, n, d_logits, s);
         if (score) score_rows(x, d_ids, n, *score, s);
@@ -515,6 +577,7 @@ class LmEngine {
     DevBuf sel_work_, sel_next_, sel_done_, sel_uni_;  // selection scratch, the next step's ids, the stop words, uniforms
     bool raw_blocks_ = false;  // ACE_MI_LM_RAW_BLOCKS at load: WF_GGML_RAW matrices are accepted and multiplied as blocks
     DevBuf raw_image_;         // the prefill's bf16 image of one raw-block matrix at a time (workspace, not weights)
+    DevBuf q_chunk_, part_chunk_;  // extend(): the chunk's Q [B][n][hq][128] f32, the chunk attention's range records
     DevBuf sc_xn_, sc_xh_, sc_work_;  // scoring: the scored rows after the final norm (f32, 16-bit), the kernel's scratch
     RopeTable rope_;  // positions 0..capacity-1
     int batch_ = 0, capacity_ = 0, len_ = 0;
@@ -639,6 +702,42 @@ ace_ggml_status ace_mi_lm_score(ace_ggml_context* ctx, const int32_t* d_ids, con
     } catch (const std::exception& ex) {
         return set_error(ctx, ACE_GGML_ERR, std::string("lm score failed: ") + ex.what());
     }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_lm_extend(ace_ggml_context* ctx, const int32_t* d_ids, const int32_t* d_mask, int32_t n,
+                                 int32_t score_from, float* d_logprob, int32_t* d_rank, float* d_logits, void* stream) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->lm) return set_error(ctx, ACE_GGML_ERR, "lm not loaded");
+    if (!d_ids || n < 1) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm extend: null pointer or n < 1");
+    if ((d_logprob == nullptr) != (d_rank == nullptr))
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm extend: d_logprob and d_rank go together");
+    const bool scoring = d_logprob != nullptr;
+    if (!scoring && !d_logits) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm extend: no output requested");
+    if (scoring && (score_from < 1 || score_from > n - 1))
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm extend: score_from must be 1..n-1");
+    acemi::LmEngine* e = lm_of(ctx);
+    if (e->batch() <= 0) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm extend: ace_mi_lm_begin was not called");
+    if (e->len() < 1) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm extend: the cache is empty");
+    if ((int64_t)e->len() + n > e->capacity())
+        return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm extend: exceeds the cache capacity");
+    try {
+        bind_device(ctx);
+        acemi::gemm_splitk_check();
+        hipStream_t s = stream ? static_cast<hipStream_t>(stream) : ctx->stream;
+        e->extend(d_ids, d_mask, n, scoring ? score_from : 0, d_logprob, d_rank, d_logits, s);
+    } catch (const std::exception& ex) {
+        return set_error(ctx, ACE_GGML_ERR, std::string("lm extend failed: ") + ex.what());
+    }
+    return ACE_GGML_OK;
+}
+
+ace_ggml_status ace_mi_lm_truncate(ace_ggml_context* ctx, int32_t len) {
+    if (!ctx) return ACE_GGML_ERR_INVALID_ARG;
+    if (!ctx->lm) return set_error(ctx, ACE_GGML_ERR, "lm not loaded");
+    acemi::LmEngine* e = lm_of(ctx);
+    if (len < 0 || len > e->len()) return set_error(ctx, ACE_GGML_ERR_INVALID_ARG, "lm truncate: len must be 0..cache_len");
+    e->truncate(len);
     return ACE_GGML_OK;
 }
 

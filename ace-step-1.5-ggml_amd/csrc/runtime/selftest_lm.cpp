@@ -551,4 +551,40 @@ ace_ggml_status ace_mi_kernel_lm_attention_shared(int32_t out_type, int32_t G, i
                               scale, q, k_cache, v_cache, key_mask, out_u16);
 }
 
+ace_ggml_status ace_mi_kernel_lm_attention_chunk(int32_t out_type, int32_t B, int32_t hq, int32_t hkv, int32_t capacity,
+                                                 int32_t past, int32_t n, float scale, const float* q,
+                                                 const uint16_t* k_cache, const uint16_t* v_cache,
+                                                 const int32_t* key_mask, uint16_t* out_u16) {
+    using namespace acemi;
+    if ((out_type != 0 && out_type != 1) || B < 1 || B > LM_MAX_BATCH || hkv < 1 || hq < 1 || hq % hkv != 0 || past < 0 ||
+        n < 1 || (int64_t)past + n > capacity || (int64_t)B * n > 65535 || !q || !k_cache || !v_cache || !key_mask || !out_u16)
+        return ACE_GGML_ERR_INVALID_ARG;
+    const int rep = hq / hkv;
+    if (rep != 1 && rep != 2 && rep != 4) return ACE_GGML_ERR_INVALID_ARG;
+    try {
+        const size_t nc = (size_t)B * hkv * capacity * D * 2, no = (size_t)B * n * hq * D * 2;
+        DevMem dq(q, (size_t)B * n * hq * D * 4), dk(k_cache, nc), dv(v_cache, nc), dm(key_mask, (size_t)B * capacity * 4);
+        DevMem dout(out_u16, no), dpart(lm_attn_chunk_part_floats(B, n, hq, past + n) * 4);
+        LmAttnChunkArgs a;
+        a.q = dq.as<float>();
+        a.k_cache = dk.as<uint16_t>();
+        a.v_cache = dv.as<uint16_t>();
+        a.key_mask = dm.as<int32_t>();
+        a.hkv = hkv;
+        a.capacity = capacity;
+        a.past = past;
+        a.n = n;
+        a.scale = scale;
+        a.out = dout.as<uint16_t>();
+        a.part = dpart.as<float>();
+        launch_lm_attention_chunk(out_type == 1 ? ActType::F16 : ActType::BF16, a, B, hq, nullptr);
+        ACEMI_HIP(hipDeviceSynchronize());
+        dout.to_host(out_u16, no);
+    } catch (const std::exception& ex) {
+        std::fprintf(stderr, "ace_mi_kernel_lm_attention_chunk: %s\n", ex.what());
+        return ACE_GGML_ERR;
+    }
+    return ACE_GGML_OK;
+}
+
 }  // extern "C"

@@ -285,6 +285,23 @@ ACE_GGML_API ace_ggml_status ace_mi_lm_forward(ace_ggml_context* ctx, const int3
 ACE_GGML_API ace_ggml_status ace_mi_lm_score(ace_ggml_context* ctx, const int32_t* d_ids, const int32_t* d_mask, int32_t n,
                                              int32_t score_from, float* d_logprob, int32_t* d_rank, float* d_logits,
                                              void* stream);
+/* A chunk of n >= 1 tokens per sequence onto a FILLED cache (cache_len >= 1), at positions cache_len .. cache_len + n - 1:
+ * the prefill's GEMMs and rounding points, attention over the fp16 cache plus the chunk itself, causal inside the chunk
+ * (kernels/lm_attn_chunk.hip: K and V read as the decode step reads them, single fp16, where the prefill reads hi + lo
+ * pairs -- the two paths agree to the last bits, not bit for bit).  d_ids / d_mask [batch][n] as in ace_mi_lm_forward.
+ * d_logprob / d_rank, both or neither: as for ace_mi_lm_score with positions counted inside the chunk, score_from in
+ * [1, n - 1] -- to score a target after a prefilled prompt, the chunk starts with the prompt's last token (see
+ * ace_mi_lm_truncate) and score_from = 1.  Both NULL: score_from is ignored.  d_logits [batch][vocab], when not NULL,
+ * gets the last position's logits; at least one output must be requested.  ACE_GGML_ERR_INVALID_ARG, cache unchanged:
+ * an empty cache, cache_len + n > capacity, score_from outside [1, n - 1] when scoring, one of d_logprob / d_rank NULL
+ * and the other not, no output, no ace_mi_lm_begin; ACE_GGML_ERR "lm not loaded" before ace_mi_load_lm. */
+ACE_GGML_API ace_ggml_status ace_mi_lm_extend(ace_ggml_context* ctx, const int32_t* d_ids, const int32_t* d_mask, int32_t n,
+                                              int32_t score_from, float* d_logprob, int32_t* d_rank, float* d_logits,
+                                              void* stream);
+/* Cache length back to len in [0, cache_len] (batch and capacity kept; the positions past len are forgotten).  A
+ * fan-out's shared-prefix reading is dropped when len is shorter than the shared length.  ACE_GGML_ERR_INVALID_ARG
+ * for any other len. */
+ACE_GGML_API ace_ggml_status ace_mi_lm_truncate(ace_ggml_context* ctx, int32_t len);
 /* Cache length back to 0 (batch and capacity kept). */
 ACE_GGML_API ace_ggml_status ace_mi_lm_reset(ace_ggml_context* ctx);
 

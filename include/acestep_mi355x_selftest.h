@@ -220,6 +220,15 @@ ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_attention_shared(int32_t out_type,
                                                                int32_t n_shared, float scale, const float* q,
                                                                const uint16_t* k_cache, const uint16_t* v_cache,
                                                                const int32_t* key_mask, uint16_t* out_u16);
+/* Chunk attention (csrc/kernels/lm_attn_chunk.hip): n query tokens per sequence at slots past .. past + n - 1 of the
+ * cache, q [B][n][hq][128] f32, row (b, t, head) over the keys j <= past + t with key_mask[b][j] != 0; out_u16
+ * [B * n][hq * 128] words of out_type.  The range workspace is allocated here.  ACE_GGML_ERR_INVALID_ARG for what the
+ * launcher refuses: past < 0, n < 1, past + n > capacity, B outside 1..8, a GQA ratio other than 1, 2, 4. */
+ACE_GGML_API ace_ggml_status ace_mi_kernel_lm_attention_chunk(int32_t out_type, int32_t B, int32_t hq, int32_t hkv,
+                                                              int32_t capacity, int32_t past, int32_t n, float scale,
+                                                              const float* q, const uint16_t* k_cache,
+                                                              const uint16_t* v_cache, const int32_t* key_mask,
+                                                              uint16_t* out_u16);
 /* Token selection (kernels/lm_sample.hip; semantics: ace_mi_lm_select in acestep_mi355x.h) on host arrays with padded
  * leading dimensions: logits [B][ld_logits] (S = B, or B / 2 when cfg_scale > 1), allowed [n_allowed] or NULL, uniform
  * [S] or NULL, seen [S][ld_seen] bytes or NULL (in-out), tokens [S * token_stride] (in-out: word s * token_stride is
